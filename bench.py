@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — fragments/sec of the MI355X per-fragment 3D path on BASELINE.json's config 2.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -96,7 +96,15 @@ def parse():
     ap.add_argument("--workload", default="cfg2", choices=["cfg2", "cfg4", "train"],
                     help="cfg2 (default) = BASELINE.json configs[1], the headline metric; cfg4 = the full "
                          "coarse-to-fine forward over 4 sequential fragments (extra measurement, no roofline)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's window) as DIR/<name>.npy, "
+                         "float32 / float64, 64 MB at most (larger arrays: a fixed seeded sample of their rows)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.scenes_per_gpu > 0:
+        ap.error("--dump-outputs goes with a single timed process per GPU, not --scenes-per-gpu")
+    return args
 
 
 def cpu_baseline(step, seconds):
@@ -510,6 +518,8 @@ def bench_cfg4(args, step, world, rank, dist, use_dist=False):
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, step.last)
     if rank == 0 and args.workload == "train":
         print(json.dumps({"metric": "train_fragments_per_sec", "value": world * args.steps / elapsed, "unit": "fragments/s",
                           "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
@@ -526,6 +536,62 @@ def bench_cfg4(args, step, world, rank, dist, use_dist=False):
                           "finest_voxels_min_max": [min(step.voxels), max(step.voxels)]}), flush=True)
     if use_dist:
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 60 << 20   # --dump-outputs: all files together (under 64 MB by either reading of MB)
+DUMP_SAMPLE_SEED = 0
+
+
+def _output_arrays(obj, name):
+    """(name, host array) for every tensor, array and number in a step's outputs, dicts and lists walked in order: floating
+    point as float32 (float64 stays), integers and booleans exactly (float32 below 2^24, float64 above); strings, None and
+    callables are skipped"""
+    import numbers
+    import re
+    import torch
+    if isinstance(obj, dict):
+        for k, v in obj.items():
+            yield from _output_arrays(v, f"{name}_{k}" if name else str(k))
+        return
+    if isinstance(obj, (list, tuple)) and not (obj and all(isinstance(v, numbers.Number) for v in obj)):
+        for i, v in enumerate(obj):
+            yield from _output_arrays(v, f"{name}_{i}")
+        return
+    if torch.is_tensor(obj):
+        obj = obj.detach().cpu().numpy()
+    if isinstance(obj, (numbers.Number, list, tuple)):
+        obj = np.asarray(obj)
+    if not isinstance(obj, np.ndarray) or obj.dtype.kind not in "biuf":
+        return
+    if obj.dtype.kind == "f":
+        dtype = obj.dtype if obj.dtype in (np.float32, np.float64) else np.float32
+    else:   # integers: float32 while every value is exact in it
+        dtype = np.float32 if obj.size == 0 or int(np.abs(obj.astype(np.int64)).max()) < 2 ** 24 else np.float64
+    yield re.sub(r"[^A-Za-z0-9_.-]", "_", name), obj.astype(dtype, copy=False)
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: every array of `outputs` (what the timed path returned for its last step) as <out_dir>/<name>.npy.  All
+    files together stay under DUMP_LIMIT_BYTES: the arrays are written smallest first, each may take an equal share of what is
+    left, and one larger than its share is replaced by a fixed sample of its rows (seed DUMP_SAMPLE_SEED, ascending row order),
+    so two runs with the same arguments write the same rows."""
+    arrays = list(_output_arrays(outputs, ""))
+    if not arrays:
+        raise SystemExit("--dump-outputs: the timed path returned no arrays")
+    left = DUMP_LIMIT_BYTES - 1024 * len(arrays)     # (a .npy header per file)
+    os.makedirs(out_dir, exist_ok=True)
+    arrays.sort(key=lambda na: na[1].nbytes)
+    for i, (name, a) in enumerate(arrays):
+        share = left // (len(arrays) - i)
+        if a.nbytes > share:
+            if a.nbytes // a.shape[0] > share:
+                a = a.reshape(-1)
+            keep = max(1, share // (a.nbytes // a.shape[0]))
+            rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.shape[0], size=keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+    return sorted(name for name, _ in arrays)
 
 
 def _fragment_digest(out):
@@ -739,6 +805,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        # the last timed step's outputs (step.flush() above completed it), before any later leg runs the step again
+        dump_outputs(args.dump_outputs, step.last)
 
     # N > 1: BASELINE.json configs[4] — the fragments of ONE scene dealt round-robin to the ranks, every fragment
     # preceded by the RCCL boundary-voxel exchange (eprecon_amd/distributed.py).  All ranks take part; reported

@@ -61,9 +61,11 @@ def build(force=False, verbose=False, out=OUT, extra_flags=None, obj_dir=CSRC, d
                 print(" ".join(cmd))
             jobs.append(cmd)
         objs.append(obj)
-    # the translation units are independent: compile them side by side
+    # the translation units are independent: compile them side by side (MAX_JOBS, when set, caps the parallel compiles:
+    # a machine's core count can be far above the CPUs this process may use)
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1) or 1) as pool:
+    workers = int(os.environ.get("MAX_JOBS") or 0) or len(os.sched_getaffinity(0))
+    with ThreadPoolExecutor(max_workers=min(len(jobs), workers) or 1) as pool:
         list(pool.map(subprocess.check_call, jobs))
     cmd = [hipcc, "--offload-arch=gfx950", "--offload-compress", "-shared", "-fPIC"] + objs + ["-o", out]
     if verbose:

@@ -19,7 +19,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 
 import ref_shim  # noqa: E402
 
-torch = ref_shim.install()
+torch = ref_shim.install(need_tree=sys.argv[1:] != ["sparse_layers"])
 
 from eprecon_amd import synthetic as S  # noqa: E402
 
@@ -618,6 +618,8 @@ def gen_sparse_layers():
     if not torch.cuda.is_available():
         print("sparse_layers: skipped — torchsparse / spconv import, but their kernels need a CUDA device")
         return False
+    if not os.path.isdir(ref_shim.REF):
+        raise RuntimeError("sparse_layers: torchsparse / spconv import, but the reference tree is not present")
     dev = torch.device("cuda")
     import models.modules as M
     from torchsparse.tensor import PointTensor

@@ -39,8 +39,8 @@ def test_inputs_are_seeded_and_machine_independent():
     assert abs(float(a["feats"].astype(np.float64).sum()) - float(b["feats"].astype(np.float64).sum())) == 0.0
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="build container only (the generator imports /root/reference)")
 def test_generator_runs_to_its_skipped_exit_or_writes_the_fixture():
+    # (the generator decides what is importable before it needs the reference tree: this runs without it)
     r = subprocess.run([sys.executable, os.path.join(GOLDEN, "make_golden.py"), "sparse_layers"], capture_output=True, text=True,
                        timeout=600, cwd=GOLDEN)
     assert r.returncode == 0, r.stderr[-2000:]
