@@ -123,6 +123,17 @@ SIGNATURES = {
     "eprecon_marching_cubes_workspace_bytes": (_sz, [_i, _i, _i]),
     "eprecon_marching_cubes_count": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),
     "eprecon_marching_cubes_emit_async": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "eprecon_marching_cubes_count_masked": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),
+    "eprecon_marching_cubes_emit_masked_async": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "eprecon_render_depth_workspace_bytes": (_sz, [_i64]),
+    "eprecon_render_depth_async": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _f, _f, _f, _i, _vp, _i64, _vp, _sz, _vp]),
+    "eprecon_depth_metrics_workspace_bytes": (_sz, [_i]),
+    "eprecon_depth_metrics_async": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _sz, _vp]),
+    "eprecon_point_bounds_async": (_i, [_vp, _i64, _vp, _vp, _vp]),
+    "eprecon_voxel_down_sample_workspace_bytes": (_sz, [_i64, _i64]),
+    "eprecon_voxel_down_sample": (_i, [_vp, _i64, _vp, _c.c_double, _vp, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "eprecon_nn_search_workspace_bytes": (_sz, [_i64, _i64]),
+    "eprecon_nn_search_async": (_i, [_vp, _i64, _vp, _i64, _vp, _c.c_double, _vp, _vp, _vp, _vp, _sz, _vp]),
     "eprecon_nearest_voxel_async": (_i, [_vp, _c.c_uint32, _vp, _i64, _vp, _i64, _i, _vp, _vp]),
     "eprecon_upsample2x_nhwc_async": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "eprecon_decoder_keys_async": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp]),

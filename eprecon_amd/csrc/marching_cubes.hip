@@ -124,11 +124,47 @@ struct McParams {
     const float *vol;
     int Dx, Dy, Dz;
     float level;
+    const float *weight;     // MASKED instantiations only: cubes with a corner of weight 0 emit nothing
 };
 
 __device__ __forceinline__ float at(const McParams &p, int x, int y, int z) { return p.vol[((size_t)x * p.Dy + y) * p.Dz + z]; }
 
+// MASKED (open3d's ExtractTriangleMesh rule): a cell takes part only when all eight corners have weight > 0; a cut edge
+// carries a vertex only when one of the (up to four) cells around it takes part.  The unmasked instantiations compile to
+// the code they always were (every `if constexpr (MASKED)` branch vanishes).
+__device__ __forceinline__ bool cell_live(const McParams &p, int x, int y, int z)
+{
+    if (x < 0 || y < 0 || z < 0 || x + 1 >= p.Dx || y + 1 >= p.Dy || z + 1 >= p.Dz) return false;
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+        ok = ok && p.weight[((size_t)(x + (k & 1)) * p.Dy + (y + ((k >> 1) & 1))) * p.Dz + (z + (k >> 2))] > 0.0f;
+    return ok;
+}
+
+__device__ __forceinline__ bool edge_live(const McParams &p, int x, int y, int z, int axis)
+{
+    const int o1 = (axis + 1) % 3, o2 = (axis + 2) % 3;
+    const int lo = o1 < o2 ? o1 : o2, hi = o1 < o2 ? o2 : o1;
+    for (int k = 0; k < 4; ++k) {
+        int q[3] = {x, y, z};
+        q[lo] -= k & 1; q[hi] -= k >> 1;
+        if (cell_live(p, q[0], q[1], q[2])) return true;
+    }
+    return false;
+}
+
+// edge (x,y,z)+axis is cut (and, when MASKED, live); the neighbour along axis must be inside the grid
+template <bool MASKED>
+__device__ __forceinline__ bool edge_cut(const McParams &p, int x, int y, int z, int axis, bool in0)
+{
+    const bool cut = (at(p, x + (axis == 0), y + (axis == 1), z + (axis == 2)) < p.level) != in0;
+    if constexpr (MASKED) return cut && edge_live(p, x, y, z, axis);
+    return cut;
+}
+
 // per grid point: number of sign-changing edges it owns (+x, +y, +z); per cell (same index, x < Dx-1 ...): triangles
+template <bool MASKED>
 __global__ __launch_bounds__(256) void mc_count_kernel(McParams p, const int8_t *table, int32_t *nvert, int32_t *ntri)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -137,12 +173,12 @@ __global__ __launch_bounds__(256) void mc_count_kernel(McParams p, const int8_t 
     const int z = i % p.Dz, y = (i / p.Dz) % p.Dy, x = i / (p.Dz * p.Dy);
     const bool in0 = at(p, x, y, z) < p.level;
     int c = 0;
-    if (x + 1 < p.Dx) c += (at(p, x + 1, y, z) < p.level) != in0;
-    if (y + 1 < p.Dy) c += (at(p, x, y + 1, z) < p.level) != in0;
-    if (z + 1 < p.Dz) c += (at(p, x, y, z + 1) < p.level) != in0;
+    if (x + 1 < p.Dx) c += edge_cut<MASKED>(p, x, y, z, 0, in0);
+    if (y + 1 < p.Dy) c += edge_cut<MASKED>(p, x, y, z, 1, in0);
+    if (z + 1 < p.Dz) c += edge_cut<MASKED>(p, x, y, z, 2, in0);
     nvert[i] = c;
     int t = 0;
-    if (x + 1 < p.Dx && y + 1 < p.Dy && z + 1 < p.Dz) {
+    if (x + 1 < p.Dx && y + 1 < p.Dy && z + 1 < p.Dz && (!MASKED || cell_live(p, x, y, z))) {
         int cs = 0;
 #pragma unroll
         for (int k = 0; k < 8; ++k) cs |= (at(p, x + (k & 1), y + ((k >> 1) & 1), z + (k >> 2)) < p.level ? 1 : 0) << k;
@@ -162,6 +198,7 @@ __device__ __forceinline__ float3 gradient(const McParams &p, int x, int y, int 
 }
 
 // vertices: one per cut edge, owned by the edge's lower grid point; order (point raster, axis x < y < z)
+template <bool MASKED>
 __global__ __launch_bounds__(256) void mc_vertex_kernel(McParams p, const int32_t *voff, float *verts, float *normals,
                                                         const int32_t *label_a, const int32_t *label_b, int32_t *out_a,
                                                         int32_t *out_b)
@@ -180,6 +217,9 @@ __global__ __launch_bounds__(256) void mc_vertex_kernel(McParams p, const int32_
         if (x1 >= p.Dx || y1 >= p.Dy || z1 >= p.Dz) continue;
         const float v1 = at(p, x1, y1, z1);
         if ((v1 < p.level) == in0) continue;
+        if constexpr (MASKED) {
+            if (!edge_live(p, x, y, z, axis)) continue;
+        }
         const float t = __fdiv_rn(p.level - v0, v1 - v0);   // linear zero crossing on the edge
         const float px = (float)x + (axis == 0 ? t : 0.0f), py = (float)y + (axis == 1 ? t : 0.0f),
                     pz = (float)z + (axis == 2 ? t : 0.0f);
@@ -203,6 +243,7 @@ __global__ __launch_bounds__(256) void mc_vertex_kernel(McParams p, const int32_
     }
 }
 
+template <bool MASKED>
 __device__ __forceinline__ int edge_vertex(const McParams &p, const int32_t *voff, int x, int y, int z, int e)
 {
     // edge e = axis * 4 + (b + 2 c): owner grid point = cell origin + (b, c) along the other two axes (ascending)
@@ -215,11 +256,12 @@ __device__ __forceinline__ int edge_vertex(const McParams &p, const int32_t *vof
     // rank of `axis` among the owner's cut edges
     const bool in0 = at(p, q[0], q[1], q[2]) < p.level;
     int r = 0;
-    if (axis > 0 && q[0] + 1 < p.Dx) r += (at(p, q[0] + 1, q[1], q[2]) < p.level) != in0;
-    if (axis > 1 && q[1] + 1 < p.Dy) r += (at(p, q[0], q[1] + 1, q[2]) < p.level) != in0;
+    if (axis > 0 && q[0] + 1 < p.Dx) r += edge_cut<MASKED>(p, q[0], q[1], q[2], 0, in0);
+    if (axis > 1 && q[1] + 1 < p.Dy) r += edge_cut<MASKED>(p, q[0], q[1], q[2], 1, in0);
     return voff[i] + r;
 }
 
+template <bool MASKED>
 __global__ __launch_bounds__(256) void mc_face_kernel(McParams p, const int8_t *table, const int32_t *voff, const int32_t *toff,
                                                       const float *verts, int32_t *faces)
 {
@@ -228,6 +270,9 @@ __global__ __launch_bounds__(256) void mc_face_kernel(McParams p, const int8_t *
     if (i >= n) return;
     const int z = i % p.Dz, y = (i / p.Dz) % p.Dy, x = i / (p.Dz * p.Dy);
     if (x + 1 >= p.Dx || y + 1 >= p.Dy || z + 1 >= p.Dz) return;
+    if constexpr (MASKED) {
+        if (!cell_live(p, x, y, z)) return;
+    }
     int cs = 0;
     float val[8];
 #pragma unroll
@@ -243,8 +288,8 @@ __global__ __launch_bounds__(256) void mc_face_kernel(McParams p, const int8_t *
     const float gz = 0.25f * ((val[4] + val[5] + val[6] + val[7]) - (val[0] + val[1] + val[2] + val[3]));
     int o = toff[i];
     for (int t = 0; t < 5 && row[3 * t] >= 0; ++t, ++o) {
-        int a = edge_vertex(p, voff, x, y, z, row[3 * t]), b = edge_vertex(p, voff, x, y, z, row[3 * t + 1]),
-            c = edge_vertex(p, voff, x, y, z, row[3 * t + 2]);
+        int a = edge_vertex<MASKED>(p, voff, x, y, z, row[3 * t]), b = edge_vertex<MASKED>(p, voff, x, y, z, row[3 * t + 1]),
+            c = edge_vertex<MASKED>(p, voff, x, y, z, row[3 * t + 2]);
         const float ax = verts[3 * (size_t)a], ay = verts[3 * (size_t)a + 1], az = verts[3 * (size_t)a + 2];
         const float ux = verts[3 * (size_t)b] - ax, uy = verts[3 * (size_t)b + 1] - ay, uz = verts[3 * (size_t)b + 2] - az;
         const float wx = verts[3 * (size_t)c] - ax, wy = verts[3 * (size_t)c + 1] - ay, wz = verts[3 * (size_t)c + 2] - az;
@@ -293,11 +338,15 @@ size_t eprecon_marching_cubes_workspace_bytes(int dx, int dy, int dz)
     return 4 * align_up(n * 4, 256) + 2 * align_up((size_t)ceil_div((int64_t)n, 2048) * 4, 256) + 256;
 }
 
-// phase 1 (blocking): counts_host[0] = vertices, [1] = triangles; the workspace keeps the scanned offsets for phase 2
-int eprecon_marching_cubes_count(const float *volume, int dx, int dy, int dz, float level, int64_t *counts_host,
-                                 void *workspace, size_t workspace_bytes, void *stream)
+}  // extern "C"
+
+namespace {
+
+template <bool MASKED>
+int mc_count(const float *volume, const float *weight, int dx, int dy, int dz, float level, int64_t *counts_host,
+             void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!volume || dx < 2 || dy < 2 || dz < 2 || !counts_host || !workspace) return EPRECON_ERR_ARG;
+    if (!volume || (MASKED && !weight) || dx < 2 || dy < 2 || dz < 2 || !counts_host || !workspace) return EPRECON_ERR_ARG;
     const int64_t n = (int64_t)dx * dy * dz;
     if (n > 0x7fffffff / 4) return EPRECON_ERR_UNSUPPORTED;
     if (workspace_bytes < eprecon_marching_cubes_workspace_bytes(dx, dy, dz)) return EPRECON_ERR_WORKSPACE;
@@ -311,8 +360,8 @@ int eprecon_marching_cubes_count(const float *volume, int dx, int dy, int dz, fl
     int32_t *voff = reinterpret_cast<int32_t *>(ws + 2 * seg), *toff = reinterpret_cast<int32_t *>(ws + 3 * seg);
     int32_t *s1 = reinterpret_cast<int32_t *>(ws + 4 * seg), *s2 = reinterpret_cast<int32_t *>(ws + 4 * seg + sseg);
     int32_t *totals = reinterpret_cast<int32_t *>(ws + 4 * seg + 2 * sseg);
-    McParams p{volume, dx, dy, dz, level};
-    hipLaunchKernelGGL(mc_count_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, p, table, nvert,
+    McParams p{volume, dx, dy, dz, level, weight};
+    hipLaunchKernelGGL(mc_count_kernel<MASKED>, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, p, table, nvert,
                        ntri);
     EP_LAUNCH_CHECK();
     rc = ep::exclusive_scan_i32(nvert, (int)n, voff, s1, totals, st);
@@ -326,13 +375,13 @@ int eprecon_marching_cubes_count(const float *volume, int dx, int dy, int dz, fl
     return EPRECON_OK;
 }
 
-// phase 2: verts f32[nv,3] (voxel coordinates, like skimage), normals f32[nv,3] or NULL, faces int32[nt,3];
-// optional per-vertex labels of the nearest voxel from two int32 volumes (semantic / instance, utils.py:236-239)
-int eprecon_marching_cubes_emit_async(const float *volume, int dx, int dy, int dz, float level, float *verts, float *normals,
-                                      int32_t *faces, const int32_t *label_a, const int32_t *label_b, int32_t *vert_label_a,
-                                      int32_t *vert_label_b, const void *workspace, void *stream)
+template <bool MASKED>
+int mc_emit(const float *volume, const float *weight, int dx, int dy, int dz, float level, float *verts, float *normals,
+            int32_t *faces, const int32_t *label_a, const int32_t *label_b, int32_t *vert_label_a, int32_t *vert_label_b,
+            const void *workspace, void *stream)
 {
-    if (!volume || !verts || !faces || !workspace || (label_a && !vert_label_a) || (label_b && !vert_label_b))
+    if (!volume || (MASKED && !weight) || !verts || !faces || !workspace || (label_a && !vert_label_a) ||
+        (label_b && !vert_label_b))
         return EPRECON_ERR_ARG;
     const int64_t n = (int64_t)dx * dy * dz;
     const int8_t *table = nullptr;
@@ -342,13 +391,52 @@ int eprecon_marching_cubes_emit_async(const float *volume, int dx, int dy, int d
     const char *ws = reinterpret_cast<const char *>(workspace);
     const size_t seg = align_up((size_t)n * 4, 256);
     const int32_t *voff = reinterpret_cast<const int32_t *>(ws + 2 * seg), *toff = reinterpret_cast<const int32_t *>(ws + 3 * seg);
-    McParams p{volume, dx, dy, dz, level};
+    McParams p{volume, dx, dy, dz, level, weight};
     const dim3 grid((unsigned)ceil_div(n, 256)), blk(256);
-    hipLaunchKernelGGL(mc_vertex_kernel, grid, blk, 0, st, p, voff, verts, normals, label_a, label_b, vert_label_a, vert_label_b);
+    hipLaunchKernelGGL(mc_vertex_kernel<MASKED>, grid, blk, 0, st, p, voff, verts, normals, label_a, label_b, vert_label_a,
+                       vert_label_b);
     EP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(mc_face_kernel, grid, blk, 0, st, p, table, voff, toff, (const float *)verts, faces);
+    hipLaunchKernelGGL(mc_face_kernel<MASKED>, grid, blk, 0, st, p, table, voff, toff, (const float *)verts, faces);
     EP_LAUNCH_CHECK();
     return EPRECON_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// phase 1 (blocking): counts_host[0] = vertices, [1] = triangles; the workspace keeps the scanned offsets for phase 2
+int eprecon_marching_cubes_count(const float *volume, int dx, int dy, int dz, float level, int64_t *counts_host,
+                                 void *workspace, size_t workspace_bytes, void *stream)
+{
+    return mc_count<false>(volume, nullptr, dx, dy, dz, level, counts_host, workspace, workspace_bytes, stream);
+}
+
+// phase 2: verts f32[nv,3] (voxel coordinates, like skimage), normals f32[nv,3] or NULL, faces int32[nt,3];
+// optional per-vertex labels of the nearest voxel from two int32 volumes (semantic / instance, utils.py:236-239)
+int eprecon_marching_cubes_emit_async(const float *volume, int dx, int dy, int dz, float level, float *verts, float *normals,
+                                      int32_t *faces, const int32_t *label_a, const int32_t *label_b, int32_t *vert_label_a,
+                                      int32_t *vert_label_b, const void *workspace, void *stream)
+{
+    return mc_emit<false>(volume, nullptr, dx, dy, dz, level, verts, normals, faces, label_a, label_b, vert_label_a,
+                          vert_label_b, workspace, stream);
+}
+
+// the same two phases restricted to the cells whose eight corners all have weight > 0 (the trimmed surface of the scene
+// evaluation: open3d's ExtractTriangleMesh rule); weight f32[dx,dy,dz] like the volume
+int eprecon_marching_cubes_count_masked(const float *volume, const float *weight, int dx, int dy, int dz, float level,
+                                        int64_t *counts_host, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return mc_count<true>(volume, weight, dx, dy, dz, level, counts_host, workspace, workspace_bytes, stream);
+}
+
+int eprecon_marching_cubes_emit_masked_async(const float *volume, const float *weight, int dx, int dy, int dz, float level,
+                                             float *verts, float *normals, int32_t *faces, const int32_t *label_a,
+                                             const int32_t *label_b, int32_t *vert_label_a, int32_t *vert_label_b,
+                                             const void *workspace, void *stream)
+{
+    return mc_emit<true>(volume, weight, dx, dy, dz, level, verts, normals, faces, label_a, label_b, vert_label_a,
+                         vert_label_b, workspace, stream);
 }
 
 }  // extern "C"

@@ -33,9 +33,11 @@ COLOR_PALETTE = np.array([
     [0, 128, 128], [128, 0, 128], [255, 128, 0], [128, 255, 0], [0, 255, 128]], dtype=np.uint8)
 
 
-def marching_cubes(volume, level=0.0, labels=()):
+def marching_cubes(volume, level=0.0, labels=(), weight=None):
     """volume f32[X,Y,Z] on the GPU -> (verts f32[N,3] voxel coordinates, faces int32[M,3], normals f32[N,3],
-    [per-vertex labels int32[N] for every int32 volume in `labels`]) as device tensors"""
+    [per-vertex labels int32[N] for every int32 volume in `labels`]) as device tensors.  weight (optional, f32[X,Y,Z]):
+    the trimmed form — no cell with a corner of weight 0 is meshed (open3d's ExtractTriangleMesh rule; the scene
+    evaluation's re-fused volume, eprecon_amd/evaluation.py)"""
     lib = _lib.load()
     if volume.device.type != "cuda":
         raise _lib.EpreconError("eprecon_amd operators need device tensors (no CPU fallback)")
@@ -44,8 +46,18 @@ def marching_cubes(volume, level=0.0, labels=()):
     dev = vol.device
     ws = torch.empty(int(lib.eprecon_marching_cubes_workspace_bytes(dx, dy, dz)), dtype=torch.uint8, device=dev)
     counts = (ctypes.c_int64 * 2)()
-    _lib.check(lib.eprecon_marching_cubes_count(_lib.ptr(vol), dx, dy, dz, float(level), ctypes.cast(counts, ctypes.c_void_p),
-                                                _lib.ptr(ws), ws.numel(), _lib.current_stream()), "eprecon_marching_cubes_count")
+    wvol = None
+    if weight is not None:
+        wvol = weight.to(device=dev, dtype=torch.float32).contiguous()
+        if wvol.shape != vol.shape:        # (the masked kernels index the weights like the volume)
+            raise ValueError(f"marching_cubes: weight shape {tuple(wvol.shape)} != volume shape {tuple(vol.shape)}")
+        _lib.check(lib.eprecon_marching_cubes_count_masked(
+            _lib.ptr(vol), _lib.ptr(wvol), dx, dy, dz, float(level), ctypes.cast(counts, ctypes.c_void_p), _lib.ptr(ws),
+            ws.numel(), _lib.current_stream()), "eprecon_marching_cubes_count_masked")
+    else:
+        _lib.check(lib.eprecon_marching_cubes_count(_lib.ptr(vol), dx, dy, dz, float(level),
+                                                    ctypes.cast(counts, ctypes.c_void_p), _lib.ptr(ws), ws.numel(),
+                                                    _lib.current_stream()), "eprecon_marching_cubes_count")
     nv, nt = int(counts[0]), int(counts[1])
     verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
     normals = torch.empty((nv, 3), dtype=torch.float32, device=dev)
@@ -55,7 +67,12 @@ def marching_cubes(volume, level=0.0, labels=()):
     outs = [torch.empty(nv, dtype=torch.int32, device=dev) for _ in labs]
     la, lb = (labs + [None, None])[:2]
     oa, ob = (outs + [None, None])[:2]
-    if nv > 0:
+    if nv > 0 and wvol is not None:
+        _lib.check(lib.eprecon_marching_cubes_emit_masked_async(
+            _lib.ptr(vol), _lib.ptr(wvol), dx, dy, dz, float(level), _lib.ptr(verts), _lib.ptr(normals), _lib.ptr(faces),
+            _lib.ptr(la), _lib.ptr(lb), _lib.ptr(oa), _lib.ptr(ob), _lib.ptr(ws), _lib.current_stream()),
+            "eprecon_marching_cubes_emit_masked_async")
+    elif nv > 0:
         _lib.check(lib.eprecon_marching_cubes_emit_async(
             _lib.ptr(vol), dx, dy, dz, float(level), _lib.ptr(verts), _lib.ptr(normals), _lib.ptr(faces), _lib.ptr(la),
             _lib.ptr(lb), _lib.ptr(oa), _lib.ptr(ob), _lib.ptr(ws), _lib.current_stream()), "eprecon_marching_cubes_emit_async")

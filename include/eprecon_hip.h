@@ -729,6 +729,66 @@ int eprecon_marching_cubes_count(const float *volume, int dx, int dy, int dz, fl
 int eprecon_marching_cubes_emit_async(const float *volume, int dx, int dy, int dz, float level, float *verts, float *normals,
                                       int32_t *faces, const int32_t *label_a, const int32_t *label_b, int32_t *vert_label_a,
                                       int32_t *vert_label_b, const void *workspace, void *stream);
+/* Trimmed form (scene evaluation, eprecon_amd/evaluation.py): the same two phases restricted to the cells whose eight
+ * corners all have weight > 0 in weight f32[dx,dy,dz] (open3d's ExtractTriangleMesh rule: a re-fused volume keeps its
+ * initial TSDF 1 where no view reached, which would otherwise mesh into a spurious copy of every surface at -sdf_trunc).
+ * A cut edge carries a vertex only when one of its (up to four) cells takes part.  Workspace: as above. */
+int eprecon_marching_cubes_count_masked(const float *volume, const float *weight, int dx, int dy, int dz, float level,
+                                        int64_t *counts_host, void *workspace, size_t workspace_bytes, void *stream);
+int eprecon_marching_cubes_emit_masked_async(const float *volume, const float *weight, int dx, int dy, int dz, float level,
+                                             float *verts, float *normals, int32_t *faces, const int32_t *label_a,
+                                             const int32_t *label_b, int32_t *vert_label_a, int32_t *vert_label_b,
+                                             const void *workspace, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Scene evaluation  (csrc/mesh_eval.hip; tools/evaluation.py + tools/evaluation_utils.py of the reference)
+ *
+ * Depth rasteriser  (replaces pyrender's OpenGL render of the predicted mesh at every camera pose)
+ *   verts f32[nv,3] (world), faces int32[nf,3]; cams f64[9 + 9 + 12 n_views] on the device: K (row-major 3x3),
+ *   K^-1, then per view the world->camera 3x4 (camera x right, y down, z forward).  depth_out f32[n_views,h,w]:
+ *   camera-frame z of the nearest surface with znear <= z <= zfar, 0 where nothing is hit.  Pixel (r, c) samples
+ *   the ray through image point (c + pixel_center, r + pixel_center).  Coverage: signs of the triple products of the
+ *   ray with the three edge planes through the camera centre (inclusive); cull_back: a face is drawn only if
+ *   ((v1-v0) x (v2-v0)) . v0_cam < 0.  Z-buffer by atomicMin on the fp32 bits: run-to-run bit-identical.
+ *   Five fixed launches for all views; workspace: eprecon_render_depth_workspace_bytes(queue_capacity).
+ * ------------------------------------------------------------------------------------------ */
+size_t eprecon_render_depth_workspace_bytes(int64_t queue_capacity);
+int eprecon_render_depth_async(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const double *cams,
+                               int n_views, int height, int width, float pixel_center, float znear, float zfar, int cull_back,
+                               float *depth_out, int64_t queue_capacity, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Depth metrics (eval_depth of tools/evaluation_utils.py, batched): pred, trgt f32[n_frames, n_pix].  sums_out
+ * f64[n_frames, 10] per frame, in a fixed order (run-to-run bit-identical): valid pixels (pred > 0, 0 < trgt < 10),
+ * pixels with pred > 0, then over the valid pixels sum |p-t|/t, |p-t|, (p-t)^2/t, (p-t)^2, (ln p - ln t)^2 and the
+ * counts of max(p/t, t/p) < 1.25, 1.25^2, 1.25^3 (fp64 per element).  workspace: _workspace_bytes(n_frames). */
+size_t eprecon_depth_metrics_workspace_bytes(int n_frames);
+int eprecon_depth_metrics_async(const float *pred, const float *trgt, int n_frames, int64_t n_pix, double *sums_out,
+                                void *workspace, size_t workspace_bytes, void *stream);
+
+/* Bounding box of a point cloud: points f32[n,3] -> out f32[6] (min xyz, max xyz) on the device; n >= 1.
+ * workspace: 256 x 6 floats (the per-block partials). */
+int eprecon_point_bounds_async(const float *points, int64_t n, float *out, float *workspace, void *stream);
+
+/* Voxel down-sample (open3d VoxelDownSample): idx = floor((p - min_bound) / voxel) in fp64, dims = the index range
+ * (from the host); out f32[<= n, 3] = the mean of every occupied voxel's points in voxel-key (x, y, z) order;
+ * *n_out_host = voxels.  The per-voxel sums are exact integer sums of 2^-36-voxel fixed-point offsets from the voxel's
+ * lowest-index point (no float atomics: bit-identical from run to run; <= 2^27 points per voxel).  Blocking (one host
+ * read per x slab).
+ * workspace: _workspace_bytes(n, slab_cells), slab_cells >= dims[1] * dims[2]. */
+size_t eprecon_voxel_down_sample_workspace_bytes(int64_t n, int64_t slab_cells);
+int eprecon_voxel_down_sample(const float *points, int64_t n, const double *min_bound_host, double voxel,
+                              const int64_t *dims_host, float *out, int64_t *n_out_host, int64_t slab_cells, void *workspace,
+                              size_t workspace_bytes, void *stream);
+
+/* Exact nearest neighbour (nn_correspondance of tools/evaluation_utils.py): for every query point the nearest
+ * reference point (squared distance in fp64, the smallest index on ties) -> idx_out int64[n_query], dist_out
+ * f32[n_query].  The reference points are bucketed into a uniform grid (lo_host, cell, dims_host from the host; every
+ * reference point inside it); each query visits shells of cells until no unvisited cell can beat its best distance.
+ * n_ref, n_query >= 1.  workspace: _workspace_bytes(n_ref, dims[0] * dims[1] * dims[2]). */
+size_t eprecon_nn_search_workspace_bytes(int64_t n_ref, int64_t n_cells);
+int eprecon_nn_search_async(const float *ref, int64_t n_ref, const float *query, int64_t n_query, const double *lo_host,
+                            double cell, const int32_t *dims_host, int64_t *idx_out, float *dist_out, void *workspace,
+                            size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Nearest finest-level voxel  (K18)
