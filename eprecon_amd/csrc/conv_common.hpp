@@ -168,10 +168,129 @@ __device__ __forceinline__ void chan_merge(float &n_a, float &mean_a, float &m2_
     n_a = n;
 }
 
+// Epilogue of the 16-row tile kernels on v_mfma_f32_16x16x4_f32 (conv3d_tile16_kernel, conv2d_tile16_kernel): lane l holds
+// output rows orow[0..3] (-1: no row) x columns 16 t + (l & 15) of its wave's CT accumulator tiles.  Bias, ReLU, residual (with
+// its pending BatchNorm), row-wise LayerNorm (16-lane xor-shuffles), the stores, and the BatchNorm summaries of the workgroup
+// (fixed-order Chan merges: lane groups, then waves) -> bn_partial row `partial_row`, and with ACC also into the accumulator block
+// of BatchNorm form (c) (p.bn_acc).  sStat: >= kWaves * 3 * 16 CT floats of LDS no wave reads any more (the caller's barrier);
+// every thread of the workgroup calls this.
+template <int CT, bool ACC = false>
+__device__ __forceinline__ void tile16_epilogue(const ConvParams &p, const f32x4 (&acc)[CT], const int (&orow)[4], float *sStat,
+                                                int partial_row)
+{
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int l16 = lane & 15, q = lane >> 4;
+    float v[CT][4];
+    bool colok[CT];
+#pragma unroll
+    for (int t = 0; t < CT; ++t) {
+        const int col = 16 * t + l16;
+        colok[t] = col < p.Cout;
+        const float b = (p.bias && colok[t]) ? p.bias[col] : 0.0f;
+        const float rs = (p.res_scale && colok[t]) ? p.res_scale[col] : 1.0f;
+        const float rb = (p.res_scale && colok[t]) ? p.res_shift[col] : 0.0f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float val = 0.0f;
+            if (colok[t] && orow[j] >= 0) {
+                val = acc[t][j] + b;
+                if (p.relu) val = fmaxf(val, 0.0f);
+                if (p.res) {
+                    float rv = p.res[(size_t)orow[j] * p.ld_res + col];
+                    if (p.res_scale) {
+                        rv = fmaf(rv, rs, rb);
+                        if (p.res_relu) rv = fmaxf(rv, 0.0f);
+                    }
+                    val += rv;
+                }
+            }
+            v[t][j] = val;
+        }
+    }
+    if (p.ln) {  // (uniform) row-wise LayerNorm over the C_out columns: 16 lanes x CT tiles hold a row
+        const float inv_c = 1.0f / (float)p.Cout;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float sum = 0.0f;
+#pragma unroll
+            for (int t = 0; t < CT; ++t) sum += v[t][j];
+#pragma unroll
+            for (int m = 8; m > 0; m >>= 1) sum += __shfl_xor(sum, m);
+            const float mean = sum * inv_c;
+            float sq = 0.0f;
+#pragma unroll
+            for (int t = 0; t < CT; ++t) {
+                const float d = colok[t] ? v[t][j] - mean : 0.0f;
+                v[t][j] = d;
+                sq = fmaf(d, d, sq);
+            }
+#pragma unroll
+            for (int m = 8; m > 0; m >>= 1) sq += __shfl_xor(sq, m);
+            const float inv = 1.0f / sqrtf(sq * inv_c + p.ln_eps);
+#pragma unroll
+            for (int t = 0; t < CT; ++t) {
+                const int col = 16 * t + l16;
+                float y = fmaf(v[t][j] * inv, (p.ln_gamma && colok[t]) ? p.ln_gamma[col] : 1.0f, (p.ln_beta && colok[t]) ? p.ln_beta[col] : 0.0f);
+                if (p.ln_post_relu) y = fmaxf(y, 0.0f);
+                v[t][j] = y;
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < CT; ++t)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (colok[t] && orow[j] >= 0) p.out[(size_t)orow[j] * p.ld_out + 16 * t + l16] = v[t][j];
+    if (p.bn_partial || (ACC && p.bn_acc)) {  // (uniform) (count, mean, M2) of the stored values per column: rows in the lane, lane groups, waves
+#pragma unroll
+        for (int t = 0; t < CT; ++t) {
+            float n = 0.0f, sum = 0.0f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (orow[j] >= 0) { n += 1.0f; sum += v[t][j]; }
+            float mean = n > 0.0f ? sum / n : 0.0f, m2 = 0.0f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (orow[j] >= 0) { const float d = v[t][j] - mean; m2 = fmaf(d, d, m2); }
+#pragma unroll
+            for (int m = 16; m < 64; m <<= 1) {  // lane groups q in order: the lower group is the left operand
+                const float on = __shfl_xor(n, m), om = __shfl_xor(mean, m), oq = __shfl_xor(m2, m);
+                const bool lower = (lane & m) == 0;
+                float a_n = lower ? n : on, a_mean = lower ? mean : om, a_m2 = lower ? m2 : oq;
+                chan_merge(a_n, a_mean, a_m2, lower ? on : n, lower ? om : mean, lower ? oq : m2);
+                n = a_n; mean = a_mean; m2 = a_m2;
+            }
+            if (q == 0) {
+                float *d = sStat + (wave * 3) * 16 * CT + 16 * t + l16;
+                d[0] = n; d[16 * CT] = mean; d[2 * 16 * CT] = m2;
+            }
+        }
+        __syncthreads();
+        if (tid < 16 * CT && tid < p.Cout) {
+            float a_n = 0.0f, a_mean = 0.0f, a_m2 = 0.0f;
+#pragma unroll
+            for (int w = 0; w < kWaves; ++w)
+                chan_merge(a_n, a_mean, a_m2, sStat[(w * 3) * 16 * CT + tid], sStat[(w * 3 + 1) * 16 * CT + tid], sStat[(w * 3 + 2) * 16 * CT + tid]);
+            if (p.bn_partial) {
+                float *dst = p.bn_partial + (size_t)partial_row * 3 * p.Cout + tid;
+                dst[0] = a_n; dst[p.Cout] = a_mean; dst[2 * p.Cout] = a_m2;
+            }
+            if (ACC && p.bn_acc) bn_acc_publish(p, tid, partial_row, partial_row == 0, a_n, a_mean, a_m2);
+        }
+    }
+}
+
 // sparse_conv_direct.hip: the long-list 3x3x3 kernel on 16x16x4 MFMAs with operands straight from L2
 bool direct16_ok(const ConvParams &p);
 constexpr int kDirectRows = 128;          // output rows (and rows of a BatchNorm summary block) per workgroup
 int launch_direct16(const ConvParams &p, hipStream_t st);
 int direct16_partial_block_rows(const ConvParams &p);   // 128, or 32 when the persistent form takes the launch
+
+// sparse_conv_tile2d.hip: the dense 2D 3x3 layers of the fusion stack on the 16-row image-tile kernel
+bool tile2d16_ok(const ConvParams &p);
+int64_t tile2d16_partial_rows(const ConvParams &p);     // one BatchNorm summary row per workgroup (image tile)
+int launch_tile2d16(const ConvParams &p, hipStream_t st);
+
 
 }  // namespace epconv

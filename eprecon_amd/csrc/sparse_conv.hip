@@ -1096,8 +1096,8 @@ __global__ __launch_bounds__(256) void conv3d_tile_narrow_kernel(ConvParams p, i
 //   B operand: W[k][16 kc + 4 q + s][16 t + (l & 15)], pre-packed so that a wave fetches (k, kc, t) with one 1 KB buffer load
 //   C / D: column l & 15, rows 4 (l >> 4) + reg
 // Summation order differs from the 32x32x2 kernels (four channels per MFMA): equal within fp32 round-off, not bit for bit.
-// Own epilogue for this accumulator layout: bias, ReLU, residual (with its pending BatchNorm), row-wise LayerNorm
-// (16-lane xor-shuffles), BatchNorm summaries (fixed-order Chan merges: lane groups, then waves).
+// Own epilogue for this accumulator layout (conv_common.hpp: tile16_epilogue, shared with the 2D twin conv2d_tile16_kernel):
+// bias, ReLU, residual (with its pending BatchNorm), row-wise LayerNorm, BatchNorm summaries.
 // ---------------------------------------------------------------------------------------------
 constexpr int kD16X = 2;                                     // tile x extent; y, z as the other tile kernels
 constexpr int kD16Halo = (kD16X + 2) * kD3HY * kD3HZ;        // 240
@@ -1261,102 +1261,7 @@ __global__ __launch_bounds__(256, 7) void conv3d_tile16_kernel(ConvParams p, int
     }
     __syncthreads();  // every wave is done with the halo: the summaries' scratch overlays it
 
-    // ---- epilogue: lane holds rows orow[0..3] x columns 16 t + l16 ----
-    float v[CT][4];
-    bool colok[CT];
-#pragma unroll
-    for (int t = 0; t < CT; ++t) {
-        const int col = 16 * t + l16;
-        colok[t] = col < p.Cout;
-        const float b = (p.bias && colok[t]) ? p.bias[col] : 0.0f;
-        const float rs = (p.res_scale && colok[t]) ? p.res_scale[col] : 1.0f;
-        const float rb = (p.res_scale && colok[t]) ? p.res_shift[col] : 0.0f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float val = 0.0f;
-            if (colok[t] && orow[j] >= 0) {
-                val = acc[t][j] + b;
-                if (p.relu) val = fmaxf(val, 0.0f);
-                if (p.res) {
-                    float rv = p.res[(size_t)orow[j] * p.ld_res + col];
-                    if (p.res_scale) {
-                        rv = fmaf(rv, rs, rb);
-                        if (p.res_relu) rv = fmaxf(rv, 0.0f);
-                    }
-                    val += rv;
-                }
-            }
-            v[t][j] = val;
-        }
-    }
-    if (p.ln) {  // (uniform) row-wise LayerNorm over the C_out columns: 16 lanes x CT tiles hold a row
-        const float inv_c = 1.0f / (float)p.Cout;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float sum = 0.0f;
-#pragma unroll
-            for (int t = 0; t < CT; ++t) sum += v[t][j];
-#pragma unroll
-            for (int m = 8; m > 0; m >>= 1) sum += __shfl_xor(sum, m);
-            const float mean = sum * inv_c;
-            float sq = 0.0f;
-#pragma unroll
-            for (int t = 0; t < CT; ++t) {
-                const float d = colok[t] ? v[t][j] - mean : 0.0f;
-                v[t][j] = d;
-                sq = fmaf(d, d, sq);
-            }
-#pragma unroll
-            for (int m = 8; m > 0; m >>= 1) sq += __shfl_xor(sq, m);
-            const float inv = 1.0f / sqrtf(sq * inv_c + p.ln_eps);
-#pragma unroll
-            for (int t = 0; t < CT; ++t) {
-                const int col = 16 * t + l16;
-                float y = fmaf(v[t][j] * inv, (p.ln_gamma && colok[t]) ? p.ln_gamma[col] : 1.0f, (p.ln_beta && colok[t]) ? p.ln_beta[col] : 0.0f);
-                if (p.ln_post_relu) y = fmaxf(y, 0.0f);
-                v[t][j] = y;
-            }
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < CT; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (colok[t] && orow[j] >= 0) p.out[(size_t)orow[j] * p.ld_out + 16 * t + l16] = v[t][j];
-    if (p.bn_partial) {  // (uniform) (count, mean, M2) of the stored values per column: rows in the lane, lane groups, waves
-#pragma unroll
-        for (int t = 0; t < CT; ++t) {
-            float n = 0.0f, sum = 0.0f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (orow[j] >= 0) { n += 1.0f; sum += v[t][j]; }
-            float mean = n > 0.0f ? sum / n : 0.0f, m2 = 0.0f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (orow[j] >= 0) { const float d = v[t][j] - mean; m2 = fmaf(d, d, m2); }
-#pragma unroll
-            for (int m = 16; m < 64; m <<= 1) {  // lane groups q in order: the lower group is the left operand
-                const float on = __shfl_xor(n, m), om = __shfl_xor(mean, m), oq = __shfl_xor(m2, m);
-                const bool lower = (lane & m) == 0;
-                float a_n = lower ? n : on, a_mean = lower ? mean : om, a_m2 = lower ? m2 : oq;
-                chan_merge(a_n, a_mean, a_m2, lower ? on : n, lower ? om : mean, lower ? oq : m2);
-                n = a_n; mean = a_mean; m2 = a_m2;
-            }
-            if (q == 0) {
-                float *d = sStat + (wave * 3) * 16 * CT + 16 * t + l16;
-                d[0] = n; d[16 * CT] = mean; d[2 * 16 * CT] = m2;
-            }
-        }
-        __syncthreads();
-        if (tid < 16 * CT && tid < p.Cout) {
-            float a_n = 0.0f, a_mean = 0.0f, a_m2 = 0.0f;
-#pragma unroll
-            for (int w = 0; w < kWaves; ++w)
-                chan_merge(a_n, a_mean, a_m2, sStat[(w * 3) * 16 * CT + tid], sStat[(w * 3 + 1) * 16 * CT + tid], sStat[(w * 3 + 2) * 16 * CT + tid]);
-            float *dst = p.bn_partial + (size_t)tile * 3 * p.Cout + tid;
-            dst[0] = a_n; dst[p.Cout] = a_mean; dst[2 * p.Cout] = a_m2;
-        }
-    }
+    tile16_epilogue<CT>(p, acc, orow, sStat, tile);
 }
 
 enum D3Kind { kD3None = 0, kD3Narrow = 1, kD3Tile16 = 2 };
@@ -2286,6 +2191,11 @@ int conv_dispatch_inner(ConvParams &p, int64_t n_in, hipStream_t st)
         }
         if (!p.nbr && p.K != 1) return EPRECON_ERR_ARG;  // dense-grid form requested for a shape it does not take, no map given
     }
+    // dense 2D 3x3 layers on long pixel lists: the 16-row image-tile kernel (sparse_conv_tile2d.hip; EPRECON_CONV_TILE2D16=0: off)
+    if (tile2d16_ok(p)) {
+        g_last_conv_kernel = "conv2d_tile16_kernel";
+        return launch_tile2d16(p, st);
+    }
     // dense 2D 3x3 layers whose caller packed the weights for it: the direct gather kernel on the pixel map
     const bool direct2d = p.K == 9 && direct16_ok(p);
     if (!direct2d) {
@@ -2551,7 +2461,7 @@ extern "C" size_t eprecon_conv_desc_workspace_bytes(const eprecon_conv_desc *d)
 
 // rows of bn_partial the launch described by `d` writes (= the nblk to hand to
 // eprecon_batchnorm_finalize_affine_async): 128-row blocks for the gather forms, image tiles for the
-// dense 2D tile kernel
+// dense 2D tile kernels
 extern "C" int64_t eprecon_conv_desc_partial_rows(const eprecon_conv_desc *d)
 {
     if (!d || d->n_out <= 0) return 0;
@@ -2562,6 +2472,7 @@ extern "C" int64_t eprecon_conv_desc_partial_rows(const eprecon_conv_desc *d)
     int64_t blocks;
     if (const int kind = conv3d_kind(p)) return d3_tiles_kind(p, kind);
     p.x_bytes = d->n_in > 0 ? ((d->n_in - 1) * (int64_t)p.ld_x + ((p.Cin + 3) & ~3)) * 4 : 0;
+    if (tile2d16_ok(p)) return tile2d16_partial_rows(p);
     if (p.K == 9 && direct16_ok(p)) return ep::ceil_div(d->n_out, (int64_t)direct16_partial_block_rows(p));
     if (conv2d_tile_ok(p, &nt, &nch, &blocks)) return blocks;
     if (wide_ok(p)) return ep::ceil_div(d->n_out, (int64_t)kWideRows);
