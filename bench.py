@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — fragments/sec of the MI355X per-fragment 3D path on BASELINE.json's config 2.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -17,11 +17,16 @@ value = N * K / max-over-ranks(time) and scaling is "weak".
 
 Prints ONE JSON line on rank 0 with the driver's keys plus
   roofline      the kernel BASELINE.json's metric names (bp_gather on the dense 96^3 / C=24 / 120x160 level), HIP-event
-                timed on its launch stream; `traffic` from the newest committed PMC passes of that kernel
-  roofline_conv one launch of the gather-GEMM convolution family (the largest share of kernel time), HIP-event timed,
-                against the dense fp32-MFMA peak
-  extra         cfg3 / cfg4 (whole NeuConNet.forward per fragment) timed in the same process, launches per fragment
+                timed on its launch stream inside the timed steps; `traffic` from the newest committed PMC passes of that kernel
+A plain run stops there: set-up, warm-up, the K timed steps, --dump-outputs, the line.  With --full the process then also runs
+what the headline does not need, and adds to the line
+  roofline_conv one launch of the gather-GEMM convolution family (the largest share of kernel time), HIP-event timed in
+                untimed extra steps, against the dense fp32-MFMA peak; `roofline_conv_family` (+ its bf16x3 opt-in) from
+                the committed per-shape times
+  extra         cfg3 / cfg4 (whole NeuConNet.forward per fragment), e2e, train and K-scenes-per-GPU legs timed in the same
+                process, launches per fragment (N > 1: the cfg5 exchange leg), with the cfg4 figures at the top level
   cpu_baseline  the CPU oracle (C + OpenMP port of the reference algorithm) on the same windows.
+--no-extra / --no-cpu-baseline drop a leg of --full.
 """
 import argparse
 import json
@@ -83,10 +88,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the legs it does not need: roofline_conv, the `extra` workloads (cfg3 / "
+                         "cfg4 / e2e / train / scenes per GPU; cfg5 with N > 1) and cpu_baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="approximate CPU time to spend on the cpu_baseline leg (rank 0, N=1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the cfg3 / cfg4 timings reported under `extra`")
+                    help="approximate CPU time to spend on the cpu_baseline leg of --full (rank 0, N=1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the timings reported under `extra`")
     ap.add_argument("--scenes-per-gpu", type=int, default=0,
                     help="with --workload cfg4: K independent scenes on ONE GPU at the same time, each in its own process with "
                          "its own NeuConNet, map handles and streams (SURVEY.md 8e: fragments of different scenes are pure "
@@ -813,7 +821,7 @@ def main():
     # preceded by the RCCL boundary-voxel exchange (eprecon_amd/distributed.py).  All ranks take part; reported
     # under `extra` (the headline stays the cfg2 metric on independent windows).
     cfg5 = None
-    if use_dist and not args.no_extra:   # (EPRECON_BENCH_FORCE_DIST=1 exercises this leg in a single-rank group)
+    if args.full and use_dist and not args.no_extra:   # (EPRECON_BENCH_FORCE_DIST=1 exercises this leg in a single-rank group)
         cfg5 = bench_cfg5(torch.device("cuda", local_rank), rank, world, dist)
 
     if rank == 0:
@@ -849,7 +857,7 @@ def main():
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
                "data": "synthetic", "config": describe, "roofline": roof}
-        if world == 1:
+        if world == 1 and args.full:
             out["roofline_conv"] = conv_roofline(step, lib)
             out["roofline_conv_family"] = conv_family_roofline()
             bfx = conv_family_roofline("conv_shapes_bf16x3.txt")      # the opt-in: beside the exact-fp32 record, priced the same way
@@ -866,7 +874,7 @@ def main():
                 out.update(fragment_summary(out["extra"]))
         elif cfg5 is not None:
             out["extra"] = cfg5
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(step, args.cpu_seconds)
         print(json.dumps(out), flush=True)
     if use_dist:

@@ -127,3 +127,13 @@ def test_scenes_per_gpu_is_a_cfg4_single_gpu_mode(monkeypatch, capsys):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--scenes-per-gpu", "2", "--workload", "train"])
     with pytest.raises(SystemExit, match="--scenes-per-gpu K goes with --workload cfg4"):
         bench.main()
+
+
+def test_plain_run_leaves_the_other_legs_to_full(monkeypatch):
+    """a plain command line is the headline alone; --full opts into the rooflines of their own runs, `extra` and cpu_baseline
+    (--no-extra / --no-cpu-baseline still drop a leg of it)"""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-extra"])
+    a = bench.parse()
+    assert a.full and a.no_extra and not a.no_cpu_baseline

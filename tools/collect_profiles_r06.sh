@@ -9,7 +9,7 @@ P=$O/profiles_r06
 rm -rf $O; mkdir -p $P
 cd /tmp && export TMPDIR=/tmp
 # 1. the driver's command + kernel statistics of the same command + PMC passes of the dominant kernel
-python $R/bench.py --steps 30 --warmup 5 > $O/bench.json 2> $O/bench.err
+python $R/bench.py --steps 30 --warmup 5 --full > $O/bench.json 2> $O/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o r -- python $R/bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extra > $O/stats.log 2>&1
 rm -f $O/stats/r_kernel_trace.csv
 for c in "FETCH_SIZE" "WRITE_SIZE" "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum" "TCC_HIT_sum TCC_MISS_sum"; do
