@@ -59,14 +59,14 @@ SIGNATURES = {
     "eprecon_batchnorm_acc_affine_async": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp]),
     "eprecon_affine_rows_acc_async": (_i, [_vp, _i64, _i, _i, _vp, _i, _i, _f, _i, _vp, _i, _vp]),
     "eprecon_affine_rows_res_async": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp]),
-    "eprecon_batchnorm_finalize_affine_async": (_i, [_vp, _i64, _i, _vp, _vp, _f, _vp, _vp, _vp]),
+    "eprecon_batchnorm_finalize_affine_async": (_i, [_vp, _i64, _i64, _i, _vp, _vp, _f, _vp, _vp, _vp]),
     "eprecon_affine_rows_async": (_i, [_vp, _i64, _i, _i, _vp, _vp, _i, _vp, _i, _vp]),
     "eprecon_pixel_map_async": (_i, [_i, _i, _i, _i, _vp, _vp]),
     "eprecon_batchnorm_apply_workspace_bytes": (_sz, [_i]),
-    "eprecon_batchnorm_apply_partials_async": (_i, [_vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _f, _vp, _i, _i, _vp, _i,
+    "eprecon_batchnorm_apply_partials_async": (_i, [_vp, _i64, _i, _i, _vp, _i64, _i64, _vp, _vp, _f, _vp, _i, _i, _vp, _i,
                                                     _vp, _vp, _vp, _sz, _vp]),
-    "eprecon_batchnorm_apply_partials_res_async": (_i, [_vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _f, _vp, _i, _vp, _vp, _i, _vp,
-                                                        _i, _vp, _sz, _vp]),
+    "eprecon_batchnorm_apply_partials_res_async": (_i, [_vp, _i64, _i, _i, _vp, _i64, _i64, _vp, _vp, _f, _vp, _i, _vp, _vp, _i,
+                                                        _vp, _i, _vp, _sz, _vp]),
     "eprecon_batchnorm_workspace_bytes": (_sz, [_i64, _i]),
     "eprecon_batchnorm_train_async": (_i, [_vp, _i64, _i, _i, _vp, _vp, _f, _vp, _i, _i, _vp, _i, _vp, _vp,
                                            _vp, _sz, _vp]),
@@ -255,7 +255,7 @@ class ConvDesc(ctypes.Structure):
                 ("relu", ctypes.c_int), ("accumulate", ctypes.c_int),
                 ("in_scale", ctypes.c_void_p), ("in_shift", ctypes.c_void_p), ("in_relu", ctypes.c_int),
                 ("res_scale", ctypes.c_void_p), ("res_shift", ctypes.c_void_p), ("res_relu", ctypes.c_int),
-                ("bn_partial", ctypes.c_void_p),
+                ("bn_partial", ctypes.c_void_p), ("bn_ld", ctypes.c_int),
                 ("ln", ctypes.c_int), ("ln_gamma", ctypes.c_void_p), ("ln_beta", ctypes.c_void_p),
                 ("ln_eps", ctypes.c_float), ("ln_post_relu", ctypes.c_int),
                 ("img_h", ctypes.c_int), ("img_w", ctypes.c_int), ("img_maps", ctypes.c_int),

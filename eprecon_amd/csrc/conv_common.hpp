@@ -17,7 +17,8 @@ struct ConvParams {
     int accumulate;      // out += result instead of out = result
     const float *res;    // optional [n_out, ld_res]: added after the ReLU (x + ReLU(conv(x)) blocks)
     int ld_res;
-    float *bn_partial;   // optional [gridDim.x][3][Cout]: per-workgroup (count, mean, M2) of the stored values
+    float *bn_partial;   // optional [3][Cout][bn_ld]: per-workgroup (count, mean, M2) of the stored values, channel-major
+    int bn_ld;           // ... its row stride (>= the summary rows the launch writes; see bn_partial_store)
     // BatchNorm of the INPUT applied while gathering: a = [relu](x * in_scale[c] + in_shift[c]) (nullptr: a = x)
     const float *in_scale, *in_shift;
     int in_relu;
@@ -168,6 +169,16 @@ __device__ __forceinline__ void chan_merge(float &n_a, float &mean_a, float &m2_
     n_a = n;
 }
 
+// One BatchNorm summary into bn_partial, channel-major: (count, mean, M2) of column `col` from summary row `row` at
+// [(q * Cout + col) * bn_ld + row], q = 0, 1, 2.  The finalize of a channel then reads three contiguous runs of rows
+// (csrc/norm.hip, bn_finalize_affine_kernel) instead of one float from each row's 64-byte segment.
+__device__ __forceinline__ void bn_partial_store(const ConvParams &p, int row, int col, float n, float mean, float m2)
+{
+    const size_t plane = (size_t)p.Cout * p.bn_ld;
+    float *dst = p.bn_partial + (size_t)col * p.bn_ld + row;
+    dst[0] = n; dst[plane] = mean; dst[2 * plane] = m2;
+}
+
 // Epilogue of the 16-row tile kernels on v_mfma_f32_16x16x4_f32 (conv3d_tile16_kernel, conv2d_tile16_kernel): lane l holds
 // output rows orow[0..3] (-1: no row) x columns 16 t + (l & 15) of its wave's CT accumulator tiles.  Bias, ReLU, residual (with
 // its pending BatchNorm), row-wise LayerNorm (16-lane xor-shuffles), the stores, and the BatchNorm summaries of the workgroup
@@ -272,10 +283,7 @@ __device__ __forceinline__ void tile16_epilogue(const ConvParams &p, const f32x4
 #pragma unroll
             for (int w = 0; w < kWaves; ++w)
                 chan_merge(a_n, a_mean, a_m2, sStat[(w * 3) * 16 * CT + tid], sStat[(w * 3 + 1) * 16 * CT + tid], sStat[(w * 3 + 2) * 16 * CT + tid]);
-            if (p.bn_partial) {
-                float *dst = p.bn_partial + (size_t)partial_row * 3 * p.Cout + tid;
-                dst[0] = a_n; dst[p.Cout] = a_mean; dst[2 * p.Cout] = a_m2;
-            }
+            if (p.bn_partial) bn_partial_store(p, partial_row, tid, a_n, a_mean, a_m2);
             if (ACC && p.bn_acc) bn_acc_publish(p, tid, partial_row, partial_row == 0, a_n, a_mean, a_m2);
         }
     }

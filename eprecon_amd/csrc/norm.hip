@@ -36,7 +36,8 @@ __device__ __forceinline__ void chan_merge(float &n_a, float &mean_a, float &m2_
 // One pass over x: block b summarises rows [b*R, (b+1)*R) with R = kBnPerThread * (256 / C); every
 // thread owns one column and <= 8 rows held in registers (two-pass mean / M2 on those, no
 // cancellation), then the (256/C) row groups are merged through LDS in fixed order.
-// partial[b][0][c] = count, [1][c] = mean, [2][c] = M2.
+// Channel-major like the convolution epilogues (conv_common.hpp, bn_partial_store): partial[(q * C + c) * nblk + b], q = 0
+// count, 1 mean, 2 M2, nblk = gridDim.x.
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float *x, int n, int C, int ld, float *partial)
 {
     __shared__ float sN[256], sMean[256], sM2[256];
@@ -79,33 +80,54 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float *x, int n, in
         __syncthreads();
     }
     if (tid < C) {
-        float *p = partial + (size_t)blockIdx.x * 3 * C;
-        p[tid] = sN[tid]; p[C + tid] = sMean[tid]; p[2 * C + tid] = sM2[tid];
+        const size_t plane = (size_t)C * gridDim.x;
+        float *p = partial + (size_t)tid * gridDim.x + blockIdx.x;
+        p[0] = sN[tid]; p[plane] = sMean[tid]; p[2 * plane] = sM2[tid];
     }
 }
 
+// Thread t's part of the merge of channel c's summaries (channel-major, partial[(q * C + c) * ld + b]): rows t, t + 256, ...
+// in order.  The rows of one loop trip — NU per thread, NU * 256 in all — are all loaded before the first is merged: the chain
+// of load latencies is what these launches cost.  Each workgroup reads three contiguous runs of nblk floats (a row-major
+// [nblk][3][C] list cost one 64-byte segment per float: 3 nblk segments through one CU).  Rows past nblk load as
+// empty summaries, which the merge skips, so NU changes the cost and not the result; bn_finalize_nu picks it.
+template <int NU>
+__device__ __forceinline__ void bn_merge_rows(const float *partial, int nblk, int64_t ld, int C, int c, int tid, float &a_n,
+                                              float &a_mean, float &a_m2)
+{
+    const float *pn = partial + (size_t)c * ld, *pm = pn + (size_t)C * ld, *pq = pm + (size_t)C * ld;
+    for (int b = tid; b < nblk; b += NU * 256) {
+        float vn[NU], vm[NU], vq[NU];
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const int bb = b + u * 256;
+            const bool ok = bb < nblk;
+            vn[u] = ok ? pn[bb] : 0.0f;
+            vm[u] = ok ? pm[bb] : 0.0f;
+            vq[u] = ok ? pq[bb] : 0.0f;
+        }
+#pragma unroll
+        for (int u = 0; u < NU; ++u) chan_merge(a_n, a_mean, a_m2, vn[u], vm[u], vq[u]);
+    }
+}
+
+// rows per thread and loop trip: the smallest of 1, 2, 4, 8, 16 that takes the list in one trip (16: registers, then a loop).
+// Empty loads and merges are not free: with NU = 16 fixed, a list of 85 rows took 4.9 us against 3.2 us (profiles/r08).
+inline int bn_finalize_nu(int64_t nblk)
+{
+    const int64_t need = (nblk + 255) / 256;
+    return need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : need <= 8 ? 8 : 16;
+}
+
 // one workgroup per channel: thread t merges partials t, t+256, ... in order, then a fixed LDS tree
-__global__ __launch_bounds__(256) void bn_finalize_kernel(const float *partial, int nblk, int C, float *mean_out,
+template <int NU>
+__global__ __launch_bounds__(256) void bn_finalize_kernel(const float *partial, int nblk, int64_t ld, int C, float *mean_out,
                                                           float *var_out)
 {
     __shared__ float sN[256], sMean[256], sM2[256];
     const int c = blockIdx.x, tid = threadIdx.x;
     float a_n = 0.0f, a_mean = 0.0f, a_m2 = 0.0f;
-    // (the summaries of four rows are loaded before the first is merged: the chain of load latencies, not the arithmetic, is
-    // what this kernel costs; the merge order — rows t, t + 256, ... — is unchanged)
-    for (int b = tid; b < nblk; b += 4 * 256) {
-        float vn[4], vm[4], vq[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int bb = b + u * 256;
-            const float *p = partial + (size_t)(bb < nblk ? bb : b) * 3 * C;
-            vn[u] = bb < nblk ? p[c] : 0.0f;
-            vm[u] = p[C + c];
-            vq[u] = p[2 * C + c];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) chan_merge(a_n, a_mean, a_m2, vn[u], vm[u], vq[u]);
-    }
+    bn_merge_rows<NU>(partial, nblk, ld, C, c, tid, a_n, a_mean, a_m2);
     sN[tid] = a_n; sMean[tid] = a_mean; sM2[tid] = a_m2;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
@@ -123,9 +145,10 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float *partial, 
 }
 
 // the same merge, published in affine form: y = x * scale + shift  ==  (x - mean) / sqrt(var + eps) * gamma + beta
-__global__ __launch_bounds__(256) void bn_finalize_affine_kernel(const float *partial, int nblk, int C, const float *gamma,
-                                                                 const float *beta, float eps, float *scale_out,
-                                                                 float *shift_out)
+template <int NU>
+__global__ __launch_bounds__(256) void bn_finalize_affine_kernel(const float *partial, int nblk, int64_t ld, int C,
+                                                                 const float *gamma, const float *beta, float eps,
+                                                                 float *scale_out, float *shift_out)
 {
     // one workgroup per channel; fixed merge order: thread t takes rows t, t + 256, ...; lanes merge by
     // xor-shuffles (lower lane first), the four wave results in wave order -- one barrier in total
@@ -135,21 +158,7 @@ __global__ __launch_bounds__(256) void bn_finalize_affine_kernel(const float *pa
     // is nothing but round trips — 37 of these sit between the layers of a cfg2 step)
     const float g_c = gamma ? gamma[c] : 1.0f, b_c = beta ? beta[c] : 0.0f;
     float a_n = 0.0f, a_mean = 0.0f, a_m2 = 0.0f;
-    // (the summaries of four rows are loaded before the first is merged: the chain of load latencies, not the arithmetic, is
-    // what this kernel costs; the merge order — rows t, t + 256, ... — is unchanged)
-    for (int b = tid; b < nblk; b += 4 * 256) {
-        float vn[4], vm[4], vq[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int bb = b + u * 256;
-            const float *p = partial + (size_t)(bb < nblk ? bb : b) * 3 * C;
-            vn[u] = bb < nblk ? p[c] : 0.0f;
-            vm[u] = p[C + c];
-            vq[u] = p[2 * C + c];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) chan_merge(a_n, a_mean, a_m2, vn[u], vm[u], vq[u]);
-    }
+    bn_merge_rows<NU>(partial, nblk, ld, C, c, tid, a_n, a_mean, a_m2);
     const int lane = tid & 63;
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) {
@@ -301,12 +310,17 @@ __global__ __launch_bounds__(256) void affine_rows_res_kernel(const float *x, in
 // 64 channels x 256 rows, the list merged once per workgroup by four row lanes with eight summary rows in flight — lost as well:
 // SPVCNN of the coarsest level 1.42 -> 1.68 ms.  The merge is a chain of dependent divisions; 74 workgroups repeating it in
 // front of their rows is slower than one 5 us launch doing it once.)
-int bn_finalize_apply(const float *x, int64_t n, int channels, int ld_x, const float *partial, int nblk,
+int bn_finalize_apply(const float *x, int64_t n, int channels, int ld_x, const float *partial, int nblk, int64_t ld,
                       const float *gamma, const float *beta, float eps, const float *residual, int ld_res,
                       int relu, float *out, int ld_out, float *mean, float *var, hipStream_t st,
                       const float *res_scale = nullptr, const float *res_shift = nullptr)
 {
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(channels), dim3(256), 0, st, partial, nblk, channels, mean, var);
+    switch (bn_finalize_nu(nblk)) {
+#define EP_FINALIZE(NU) \
+    case NU: hipLaunchKernelGGL(bn_finalize_kernel<NU>, dim3(channels), dim3(256), 0, st, partial, nblk, ld, channels, mean, var); break
+        EP_FINALIZE(1); EP_FINALIZE(2); EP_FINALIZE(4); EP_FINALIZE(8); EP_FINALIZE(16);
+#undef EP_FINALIZE
+    }
     EP_LAUNCH_CHECK();
     const size_t total = (size_t)n * channels;
     hipLaunchKernelGGL(bn_apply_kernel, dim3((unsigned)ceil_div((int64_t)total, 256)), dim3(256), 0, st, x,
@@ -352,7 +366,7 @@ int eprecon_batchnorm_train_async(const float *x, int64_t n, int channels, int l
     float *var = var_out ? var_out : reinterpret_cast<float *>(ws);
     hipLaunchKernelGGL(bn_stats_kernel, dim3(nblk), dim3(256), 0, st, x, (int)n, channels, ld_x, partial);
     EP_LAUNCH_CHECK();
-    return bn_finalize_apply(x, n, channels, ld_x, partial, nblk, gamma, beta, eps, residual, ld_res, relu, out,
+    return bn_finalize_apply(x, n, channels, ld_x, partial, nblk, nblk, gamma, beta, eps, residual, ld_res, relu, out,
                              ld_out, mean, var, st);
 }
 
@@ -363,15 +377,15 @@ size_t eprecon_batchnorm_apply_workspace_bytes(int channels)
 
 // Second half of the train-mode BatchNorm for a tensor whose per-block (count, mean, M2) summaries
 // were already produced by its producer (eprecon_sparse_conv_fused_async's bn_partial,
-// [nblk][3][channels]): fixed-order merge -> mean / biased variance -> affine [+ residual] [ReLU].
+// [3][channels][ld], ld >= nblk): fixed-order merge -> mean / biased variance -> affine [+ residual] [ReLU].
 int eprecon_batchnorm_apply_partials_async(const float *x, int64_t n, int channels, int ld_x,
-                                           const float *partial, int64_t nblk, const float *gamma,
+                                           const float *partial, int64_t nblk, int64_t ld, const float *gamma,
                                            const float *beta, float eps, const float *residual,
                                            int ld_res, int relu, float *out, int ld_out, float *mean_out,
                                            float *var_out, void *workspace, size_t workspace_bytes,
                                            void *stream)
 {
-    if (!x || !out || !partial || n < 0 || nblk <= 0 || nblk > 0x7fffffff || channels <= 0 || ld_x < channels ||
+    if (!x || !out || !partial || n < 0 || nblk <= 0 || nblk > 0x7fffffff || ld < nblk || channels <= 0 || ld_x < channels ||
         ld_out < channels || !workspace)
         return EPRECON_ERR_ARG;
     if (workspace_bytes < eprecon_batchnorm_apply_workspace_bytes(channels)) return EPRECON_ERR_WORKSPACE;
@@ -380,17 +394,17 @@ int eprecon_batchnorm_apply_partials_async(const float *x, int64_t n, int channe
     float *mean = mean_out ? mean_out : reinterpret_cast<float *>(ws);
     ws += align_up((size_t)channels * sizeof(float), 256);
     float *var = var_out ? var_out : reinterpret_cast<float *>(ws);
-    return bn_finalize_apply(x, n, channels, ld_x, partial, (int)nblk, gamma, beta, eps, residual, ld_res, relu,
+    return bn_finalize_apply(x, n, channels, ld_x, partial, (int)nblk, ld, gamma, beta, eps, residual, ld_res, relu,
                              out, ld_out, mean, var, (hipStream_t)stream);
 }
 
 int eprecon_batchnorm_apply_partials_res_async(const float *x, int64_t n, int channels, int ld_x, const float *partial,
-                                               int64_t nblk, const float *gamma, const float *beta, float eps,
+                                               int64_t nblk, int64_t ld, const float *gamma, const float *beta, float eps,
                                                const float *residual, int ld_res, const float *res_scale,
                                                const float *res_shift, int relu, float *out, int ld_out, void *workspace,
                                                size_t workspace_bytes, void *stream)
 {
-    if (!x || !out || !partial || !residual || !res_scale || !res_shift || n < 0 || nblk <= 0 || nblk > 0x7fffffff ||
+    if (!x || !out || !partial || !residual || !res_scale || !res_shift || n < 0 || nblk <= 0 || nblk > 0x7fffffff || ld < nblk ||
         channels <= 0 || ld_x < channels || ld_out < channels || ld_res < channels || !workspace)
         return EPRECON_ERR_ARG;
     if (workspace_bytes < eprecon_batchnorm_apply_workspace_bytes(channels)) return EPRECON_ERR_WORKSPACE;
@@ -398,17 +412,25 @@ int eprecon_batchnorm_apply_partials_res_async(const float *x, int64_t n, int ch
     char *ws = reinterpret_cast<char *>(workspace);
     float *mean = reinterpret_cast<float *>(ws);
     float *var = reinterpret_cast<float *>(ws + align_up((size_t)channels * sizeof(float), 256));
-    return bn_finalize_apply(x, n, channels, ld_x, partial, (int)nblk, gamma, beta, eps, residual, ld_res, relu, out, ld_out,
+    return bn_finalize_apply(x, n, channels, ld_x, partial, (int)nblk, ld, gamma, beta, eps, residual, ld_res, relu, out, ld_out,
                              mean, var, (hipStream_t)stream, res_scale, res_shift);
 }
 
-int eprecon_batchnorm_finalize_affine_async(const float *partial, int64_t nblk, int channels, const float *gamma,
+int eprecon_batchnorm_finalize_affine_async(const float *partial, int64_t nblk, int64_t ld, int channels, const float *gamma,
                                             const float *beta, float eps, float *scale_out, float *shift_out,
                                             void *stream)
 {
-    if (!partial || !scale_out || !shift_out || nblk <= 0 || nblk > 0x7fffffff || channels <= 0) return EPRECON_ERR_ARG;
-    hipLaunchKernelGGL(bn_finalize_affine_kernel, dim3(channels), dim3(256), 0, (hipStream_t)stream, partial, (int)nblk,
-                       channels, gamma, beta, eps, scale_out, shift_out);
+    if (!partial || !scale_out || !shift_out || nblk <= 0 || nblk > 0x7fffffff || ld < nblk || channels <= 0) return EPRECON_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    switch (bn_finalize_nu(nblk)) {
+#define EP_FINALIZE(NU)                                                                                                            \
+    case NU:                                                                                                                       \
+        hipLaunchKernelGGL(bn_finalize_affine_kernel<NU>, dim3(channels), dim3(256), 0, st, partial, (int)nblk, ld, channels, gamma, \
+                           beta, eps, scale_out, shift_out);                                                                         \
+        break
+        EP_FINALIZE(1); EP_FINALIZE(2); EP_FINALIZE(4); EP_FINALIZE(8); EP_FINALIZE(16);
+#undef EP_FINALIZE
+    }
     EP_LAUNCH_CHECK();
     return EPRECON_OK;
 }

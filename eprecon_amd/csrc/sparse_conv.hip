@@ -256,10 +256,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams &p, f32x16 (&acc)
             for (int w = 0; w < kWaves; ++w)
                 chan_merge(a_n, a_mean, a_m2, sStat[(w * 3) * TN + tid], sStat[(w * 3 + 1) * TN + tid],
                            sStat[(w * 3 + 2) * TN + tid]);
-            if (!ACC || p.bn_partial) {
-                float *dst = p.bn_partial + (size_t)partial_row * 3 * p.Cout + col0 + tid;
-                dst[0] = a_n; dst[p.Cout] = a_mean; dst[2 * p.Cout] = a_m2;
-            }
+            if (!ACC || p.bn_partial) bn_partial_store(p, partial_row, col0 + tid, a_n, a_mean, a_m2);
             if (ACC && p.bn_acc) bn_acc_publish(p, col0 + tid, partial_row, partial_row == 0, a_n, a_mean, a_m2);
         }
     }
@@ -1026,10 +1023,7 @@ __global__ __launch_bounds__(256) void conv3d_tile_narrow_kernel(ConvParams p, i
         sWn[e] = c < p.Cin ? p.w[((size_t)k * p.Cin + c) * p.Cout] : 0.0f;
     }
     if (!d3_stage_halo<NCH, WV>(p, x0, y0, z0, sX, tid, p.debug)) {  // (its barriers also publish sWn)
-        if (p.bn_partial && tid == 0) {
-            float *dst = p.bn_partial + (size_t)tile * 3 * p.Cout;
-            dst[0] = 0.0f; dst[p.Cout] = 0.0f; dst[2 * p.Cout] = 0.0f;
-        }
+        if (p.bn_partial && tid == 0) bn_partial_store(p, tile, 0, 0.0f, 0.0f, 0.0f);
         return;
     }
     const int v = tid >> 1, part = tid & 1;  // cell (x = v / 32, y = (v / 8) % 4, z = v % 8), half of the channel groups
@@ -1080,8 +1074,7 @@ __global__ __launch_bounds__(256) void conv3d_tile_narrow_kernel(ConvParams p, i
         if (tid == 0) {
             float a_n = 0.0f, a_mean = 0.0f, a_m2 = 0.0f;
             for (int w = 0; w < kWaves; ++w) chan_merge(a_n, a_mean, a_m2, sRed[w * 3], sRed[w * 3 + 1], sRed[w * 3 + 2]);
-            float *dst = p.bn_partial + (size_t)tile * 3 * p.Cout;
-            dst[0] = a_n; dst[p.Cout] = a_mean; dst[2 * p.Cout] = a_m2;
+            bn_partial_store(p, tile, 0, a_n, a_mean, a_m2);
         }
     }
 }
@@ -1182,10 +1175,7 @@ __global__ __launch_bounds__(256, 7) void conv3d_tile16_kernel(ConvParams p, int
     float *sStat = sX;  // (after the loop) [4 waves][3][16 CT] summaries
 
     if (!d3_stage_ranks<NCH, kD16X, 256>(p, x0, y0, z0, sX, tid)) {
-        if (p.bn_partial && tid < 16 * CT && tid < p.Cout) {
-            float *dst = p.bn_partial + (size_t)tile * 3 * p.Cout + tid;
-            dst[0] = 0.0f; dst[p.Cout] = 0.0f; dst[2 * p.Cout] = 0.0f;
-        }
+        if (p.bn_partial && tid < 16 * CT && tid < p.Cout) bn_partial_store(p, tile, tid, 0.0f, 0.0f, 0.0f);
         return;
     }
     // wave -> (x = wave / 2, y pair = wave % 2); MFMA row r -> cell (y = 2 (wave % 2) + r / 8, z = r % 8)
@@ -2387,7 +2377,7 @@ static void params_from_desc(ConvParams &p, const eprecon_conv_desc *d)
     p.x = d->x; p.nbr = d->nbr; p.w = d->weight; p.bias = d->bias; p.out = d->out;
     p.K = d->kvol; p.Cin = d->cin; p.Cout = d->cout; p.ld_x = d->ld_x; p.ld_out = d->ld_out;
     p.relu = d->relu; p.accumulate = d->accumulate;
-    p.res = d->residual; p.ld_res = d->ld_res; p.bn_partial = d->bn_partial;
+    p.res = d->residual; p.ld_res = d->ld_res; p.bn_partial = d->bn_partial; p.bn_ld = d->bn_ld;
     p.in_scale = d->in_scale; p.in_shift = d->in_shift; p.in_relu = d->in_relu;
     p.res_scale = d->res_scale; p.res_shift = d->res_shift; p.res_relu = d->res_relu;
     p.ln = d->ln; p.ln_gamma = d->ln_gamma; p.ln_beta = d->ln_beta; p.ln_eps = d->ln_eps;
@@ -2424,12 +2414,19 @@ extern "C" int eprecon_conv_desc_takes_bn_acc(const eprecon_conv_desc *d)
     return !p.ln && !p.accumulate && bn_acc_family(p) ? 1 : 0;
 }
 
+extern "C" int64_t eprecon_conv_desc_partial_rows(const eprecon_conv_desc *d);
+
 extern "C" int eprecon_conv_desc_async(const eprecon_conv_desc *d, void *stream)
 {
     if (!d) return EPRECON_ERR_ARG;
     ConvParams p = {};
     params_from_desc(p, d);
     p.n_out = (int)(d->n_out > 0 && d->n_out <= 0x7fffffff ? d->n_out : 0);
+    if (p.bn_partial) {     // row stride of the channel-major summaries: at least the rows this launch writes
+        const int64_t rows = eprecon_conv_desc_partial_rows(d);
+        if (p.bn_ld == 0) p.bn_ld = (int)(rows > 0 ? rows : 1);
+        if (p.bn_ld < rows) return EPRECON_ERR_ARG;
+    }
     if (p.bn_acc && (p.bn_acc_ld <= 0 || p.bn_acc_c0 < 0 || p.bn_acc_c0 + p.Cout > p.bn_acc_ld || p.ln || p.accumulate || !bn_acc_family(p)))
         return EPRECON_ERR_ARG;        // (ask eprecon_conv_desc_takes_bn_acc first)
     if (p.in_acc) {
@@ -2495,6 +2492,7 @@ extern "C" int eprecon_sparse_conv_fused_async(const float *x, int64_t n_in, int
     p.K = kvol; p.Cin = cin; p.Cout = cout; p.ld_x = ld_x; p.ld_out = ld_out;
     p.relu = relu; p.accumulate = accumulate;
     p.res = residual; p.ld_res = ld_res; p.bn_partial = bn_partial;
+    p.bn_ld = (int)ep::ceil_div(n_out > 0 ? n_out : 1, (int64_t)kRowsPerBlock);   // (no flex_partial: 128-row blocks only)
     return conv_check_and_run(p, n_in, n_out, stream);
 }
 

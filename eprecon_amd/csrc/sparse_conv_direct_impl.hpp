@@ -199,10 +199,7 @@ __device__ __forceinline__ void direct_epilogue(const ConvParams &p, f32x4 (&acc
             }
             if constexpr (PERWAVE) {
                 if (q == 0 && colok[t]) {
-                    if (p.bn_partial) {
-                        float *dst = p.bn_partial + (size_t)block * 3 * p.Cout + 16 * t + l16;
-                        dst[0] = n; dst[p.Cout] = mean; dst[2 * p.Cout] = m2;
-                    }
+                    if (p.bn_partial) bn_partial_store(p, block, 16 * t + l16, n, mean, m2);
                     if (p.bn_acc) bn_acc_publish(p, 16 * t + l16, block, block == 0, n, mean, m2);
                 }
                 continue;
@@ -219,10 +216,7 @@ __device__ __forceinline__ void direct_epilogue(const ConvParams &p, f32x4 (&acc
 #pragma unroll
             for (int w = 0; w < kWaves; ++w)
                 chan_merge(a_n, a_mean, a_m2, sStat[(w * 3) * 16 * CT + tid], sStat[(w * 3 + 1) * 16 * CT + tid], sStat[(w * 3 + 2) * 16 * CT + tid]);
-            if (p.bn_partial) {
-                float *dst = p.bn_partial + (size_t)blockIdx.x * 3 * p.Cout + tid;
-                dst[0] = a_n; dst[p.Cout] = a_mean; dst[2 * p.Cout] = a_m2;
-            }
+            if (p.bn_partial) bn_partial_store(p, (int)blockIdx.x, tid, a_n, a_mean, a_m2);
             if (p.bn_acc) bn_acc_publish(p, tid, (int)blockIdx.x, blockIdx.x == 0, a_n, a_mean, a_m2);
         }
     }

@@ -146,8 +146,9 @@ struct Pass {
         }
         int64_t rows_p = eprecon_conv_desc_partial_rows(&c);
         if (rows_p < 1) rows_p = 1;
-        float *partial = static_cast<float *>(alloc((size_t)rows_p * 3 * w.cout * sizeof(float)));
+        float *partial = static_cast<float *>(alloc((size_t)rows_p * 3 * w.cout * sizeof(float)));   // [3][cout][rows_p]
         c.bn_partial = partial;
+        c.bn_ld = (int)rows_p;
         *n_partial = rows_p;
         if (!dry && ok() && n_out > 0) step(eprecon_conv_desc_async(&c, stream));
         if (need) release(c.workspace);
@@ -159,7 +160,7 @@ struct Pass {
         const eprecon_spvcnn_conv &w = d->conv[s];
         float *aff = static_cast<float *>(alloc((size_t)2 * w.cout * sizeof(float)));
         if (!dry && ok())
-            step(eprecon_batchnorm_finalize_affine_async(partial, rows_p, w.cout, d->bn[s].gamma, d->bn[s].beta, d->bn[s].eps, aff,
+            step(eprecon_batchnorm_finalize_affine_async(partial, rows_p, rows_p, w.cout, d->bn[s].gamma, d->bn[s].beta, d->bn[s].eps, aff,
                                                          aff + w.cout, stream));
         return aff;
     }
@@ -172,11 +173,11 @@ struct Pass {
         struct Done { Pass *p; void *ws; ~Done() { p->release(ws); } } done{this, ws};
         if (dry || !ok()) return;
         if (res_aff)
-            step(eprecon_batchnorm_apply_partials_res_async(x.p, x.n, c, x.ld, partial, rows_p, d->bn[s].gamma, d->bn[s].beta,
+            step(eprecon_batchnorm_apply_partials_res_async(x.p, x.n, c, x.ld, partial, rows_p, rows_p, d->bn[s].gamma, d->bn[s].beta,
                                                             d->bn[s].eps, res->p, res->ld, res_aff, res_aff + c, 1, out.p, out.ld, ws,
                                                             wsb, stream));
         else
-            step(eprecon_batchnorm_apply_partials_async(x.p, x.n, c, x.ld, partial, rows_p, d->bn[s].gamma, d->bn[s].beta,
+            step(eprecon_batchnorm_apply_partials_async(x.p, x.n, c, x.ld, partial, rows_p, rows_p, d->bn[s].gamma, d->bn[s].beta,
                                                         d->bn[s].eps, res ? res->p : nullptr, res ? res->ld : 0, 1, out.p, out.ld,
                                                         nullptr, nullptr, ws, wsb, stream));
     }

@@ -248,11 +248,12 @@ def conv_bn_launch(w, bias, gamma, beta, eps, k, x, grid, out=None, aff=None, re
         aff = (a[0], a[1])
     assert not isinstance(aff, AccSlice), "an accumulator slice was handed to a launch that cannot produce into it"
     # the summaries are per workgroup: 128-row blocks (gather forms) or image tiles (tile kernel)
-    partial = torch.empty((lib.eprecon_conv_desc_partial_rows(ctypes.byref(d)), 3, cout), dtype=torch.float32, device=dev)
-    d.bn_partial = partial.data_ptr()
+    partial = SP.bn_summaries(lib.eprecon_conv_desc_partial_rows(ctypes.byref(d)), cout, dev)
+    nblk, ld = SP.summary_layout(partial)
+    d.bn_partial, d.bn_ld = partial.data_ptr(), ld
     _lib.check(lib.eprecon_conv_desc_async(ctypes.byref(d), _lib.current_stream()), "eprecon_conv_desc_async")
     _lib.check(lib.eprecon_batchnorm_finalize_affine_async(
-        partial.data_ptr(), partial.shape[0], cout, _dptr(gamma), _dptr(beta), float(eps),
+        partial.data_ptr(), nblk, ld, cout, _dptr(gamma), _dptr(beta), float(eps),
         aff[0].data_ptr(), aff[1].data_ptr(), _lib.current_stream()), "eprecon_batchnorm_finalize_affine_async")
     return Act(out, aff[0], aff[1], relu)
 

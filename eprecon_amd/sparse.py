@@ -500,10 +500,25 @@ def sparse_conv(x, weight, nbr=None, bias=None, out=None, relu=False, accumulate
     return out
 
 
+def bn_summaries(rows, cout, device):
+    """a buffer for the per-workgroup BatchNorm summaries of `rows` workgroups: stored channel-major, f32[3, cout, rows] (what
+    the finalize reads as three contiguous runs per channel), handed out as the logical [rows, 3, cout] view"""
+    return torch.empty((3, cout, max(int(rows), 1)), dtype=torch.float32, device=device).permute(2, 0, 1)
+
+
+def summary_layout(partial):
+    """(nblk, ld) of a [rows, 3, C] summary view over channel-major storage (bn_summaries); asserts that layout"""
+    nblk, three, c = partial.shape
+    s0, s1, s2 = partial.stride()
+    assert three == 3 and partial.dtype == torch.float32 and s0 == 1 and s2 >= nblk and s1 == c * s2, \
+        "BatchNorm summaries must be the channel-major view bn_summaries() returns"
+    return nblk, s2
+
+
 def sparse_conv_fused(x, weight, nbr=None, bias=None, out=None, relu=False, residual=None, accumulate=False,
                       bn_partial=False):
     """sparse_conv with the fused epilogues: v = conv + bias [+ out]; [relu]; [+ residual]; and, with
-    bn_partial, the per-workgroup BatchNorm summaries f32[ceil(n/128), 3, cout] of the stored values.
+    bn_partial, the per-workgroup BatchNorm summaries [ceil(n/128), 3, cout] of the stored values (a bn_summaries view).
     Returns (out, partial or None)."""
     lib = _lib.load()
     w_owner = weight
@@ -534,9 +549,8 @@ def sparse_conv_fused(x, weight, nbr=None, bias=None, out=None, relu=False, resi
         keep.append(_attach_workspace(d, x.device))
         partial = None
         if bn_partial:
-            partial = torch.empty((max(int(lib.eprecon_conv_desc_partial_rows(ctypes.byref(d))), 1), 3, cout),
-                                  dtype=torch.float32, device=x.device)
-            d.bn_partial = partial.data_ptr()
+            partial = bn_summaries(lib.eprecon_conv_desc_partial_rows(ctypes.byref(d)), cout, x.device)
+            d.bn_partial, d.bn_ld = partial.data_ptr(), summary_layout(partial)[1]
         _lib.check(lib.eprecon_conv_desc_async(ctypes.byref(d), _lib.current_stream()), "eprecon_conv_desc_async")
         del keep
         return out, partial
@@ -547,7 +561,7 @@ def sparse_conv_fused(x, weight, nbr=None, bias=None, out=None, relu=False, resi
     assert out.shape == (n_out, cout)
     partial = None
     if bn_partial:
-        partial = torch.empty(((n_out + 127) // 128, 3, cout), dtype=torch.float32, device=x.device)
+        partial = bn_summaries((n_out + 127) // 128, cout, x.device)    # (the library's stride: ceil(n_out / 128))
     if residual is not None:
         assert residual.shape == (n_out, cout) and residual.dtype == torch.float32
     _lib.check(lib.eprecon_sparse_conv_fused_async(
@@ -627,9 +641,8 @@ def conv_stats(x, weight, nbr=None, in_affine=None, out=None, bias=None):
     if in_affine is not None:
         d.in_scale, d.in_shift, d.in_relu = in_affine[0].data_ptr(), in_affine[1].data_ptr(), int(in_affine[2])
     keep.append(_attach_workspace(d, x.device))
-    rows = max(int(lib.eprecon_conv_desc_partial_rows(ctypes.byref(d))), 1)
-    partial = torch.empty((rows, 3, cout), dtype=torch.float32, device=x.device)
-    d.bn_partial = partial.data_ptr()
+    partial = bn_summaries(lib.eprecon_conv_desc_partial_rows(ctypes.byref(d)), cout, x.device)
+    d.bn_partial, d.bn_ld = partial.data_ptr(), summary_layout(partial)[1]
     if n_out > 0:
         _lib.check(lib.eprecon_conv_desc_async(ctypes.byref(d), _lib.current_stream()), "eprecon_conv_desc_async")
     return out, partial
@@ -639,9 +652,10 @@ def bn_affine(partial, gamma, beta, eps):
     """summaries -> the BatchNorm in affine form (scale, shift), to be applied by a consumer on load"""
     lib = _lib.load()
     c = partial.shape[2]
+    nblk, ld = summary_layout(partial)
     aff = torch.empty((2, c), dtype=torch.float32, device=partial.device)
     _lib.check(lib.eprecon_batchnorm_finalize_affine_async(
-        partial.data_ptr(), partial.shape[0], c, _lib.ptr(gamma), _lib.ptr(beta), float(eps), aff[0].data_ptr(),
+        partial.data_ptr(), nblk, ld, c, _lib.ptr(gamma), _lib.ptr(beta), float(eps), aff[0].data_ptr(),
         aff[1].data_ptr(), _lib.current_stream()), "eprecon_batchnorm_finalize_affine_async")
     return aff[0], aff[1]
 
@@ -652,7 +666,8 @@ def batchnorm_apply_partials(x, partial, gamma=None, beta=None, eps=1e-5, residu
     res_affine = (scale, shift): the residual carries a pending BatchNorm of its own, applied on load"""
     lib = _lib.load()
     n, c = x.shape
-    assert partial.shape[1:] == (3, c) and partial.is_contiguous()
+    assert partial.shape[1:] == (3, c)
+    nblk, ld = summary_layout(partial)
     if out is None:
         out = torch.empty((n, c), dtype=torch.float32, device=x.device)
     # mean / var scratch is a per-call buffer (not the shared grow-only workspace): independent branches
@@ -660,12 +675,12 @@ def batchnorm_apply_partials(x, partial, gamma=None, beta=None, eps=1e-5, residu
     ws = torch.empty((lib.eprecon_batchnorm_apply_workspace_bytes(c),), dtype=torch.uint8, device=x.device)
     if res_affine is not None:
         _lib.check(lib.eprecon_batchnorm_apply_partials_res_async(
-            _lib.ptr(x), n, c, _ld(x), _lib.ptr(partial), partial.shape[0], _lib.ptr(gamma), _lib.ptr(beta), float(eps),
+            _lib.ptr(x), n, c, _ld(x), _lib.ptr(partial), nblk, ld, _lib.ptr(gamma), _lib.ptr(beta), float(eps),
             _lib.ptr(residual), _ld(residual), _lib.ptr(res_affine[0]), _lib.ptr(res_affine[1]), int(relu), _lib.ptr(out),
             _ld(out), _lib.ptr(ws), ws.numel(), _lib.current_stream()), "eprecon_batchnorm_apply_partials_res_async")
         return out
     _lib.check(lib.eprecon_batchnorm_apply_partials_async(
-        _lib.ptr(x), n, c, _ld(x), _lib.ptr(partial), partial.shape[0], _lib.ptr(gamma), _lib.ptr(beta),
+        _lib.ptr(x), n, c, _ld(x), _lib.ptr(partial), nblk, ld, _lib.ptr(gamma), _lib.ptr(beta),
         float(eps), _lib.ptr(residual), _ld(residual) if residual is not None else 0, int(relu), _lib.ptr(out),
         _ld(out), None, None, _lib.ptr(ws), ws.numel(), _lib.current_stream()),
         "eprecon_batchnorm_apply_partials_async")

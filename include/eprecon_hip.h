@@ -246,9 +246,10 @@ int eprecon_sparse_conv_async(const float *x, int64_t n_in, int ld_x, const int3
  *   v = conv + bias [+ out]; [v = relu(v)]; [v += residual];  out = v
  * (residual: BN(x + ReLU(conv(x))) blocks, models/modules.py:385-399), and optionally the first
  * half of the train-mode BatchNorm that follows (models/modules.py:372-383 and every
- * spnn.BatchNorm): bn_partial f32[ceil(n_out/128)][3][cout] receives per-workgroup
- * (count, mean, M2) summaries of the stored values (eprecon_conv_bn_partial_bytes bytes), to be
- * finished by eprecon_batchnorm_apply_partials_async without re-reading the tensor for statistics.
+ * spnn.BatchNorm): bn_partial f32[3][cout][nblk], nblk = ceil(n_out/128), receives per-workgroup
+ * (count, mean, M2) summaries of the stored values, channel-major (eprecon_conv_bn_partial_bytes bytes),
+ * to be finished by eprecon_batchnorm_apply_partials_async (ld = nblk) without re-reading the tensor
+ * for statistics.
  */
 size_t eprecon_conv_bn_partial_bytes(int64_t n_out, int cout);
 int eprecon_sparse_conv_fused_async(const float *x, int64_t n_in, int ld_x, const int32_t *nbr, int kvol,
@@ -278,7 +279,9 @@ typedef struct eprecon_conv_desc {
     int relu; int accumulate;
     const float *in_scale; const float *in_shift; int in_relu;
     const float *res_scale; const float *res_shift; int res_relu;
-    float *bn_partial;
+    /* ... channel-major: (count, mean, M2) of column c from summary row r at bn_partial[(q * cout + c) * bn_ld + r], q = 0, 1, 2;
+     * bn_ld >= eprecon_conv_desc_partial_rows(desc), 0 = exactly that many */
+    float *bn_partial; int bn_ld;
     /* row-wise LayerNorm over the cout channels after bias / ReLU / residual (the spconv + LayerNorm
      * blocks of models/modules.py:447-452,473-482, models/occupancy_initialization.py:141-169):
      * out = [relu]( LN(v) * ln_gamma + ln_beta ); cout <= 128, excludes bn_partial / accumulate */
@@ -338,8 +341,9 @@ int eprecon_conv_desc_async(const eprecon_conv_desc *desc, void *stream);
 size_t eprecon_conv_desc_workspace_bytes(const eprecon_conv_desc *desc);
 /* number of bn_partial rows the launch described by desc writes (nblk of the finalize call) */
 int64_t eprecon_conv_desc_partial_rows(const eprecon_conv_desc *desc);
-/* producer-side summaries partial f32[nblk][3][channels] -> the BatchNorm in affine form */
-int eprecon_batchnorm_finalize_affine_async(const float *partial, int64_t nblk, int channels, const float *gamma,
+/* producer-side summaries partial f32[3][channels][ld] (row r of channel c: partial[(q * channels + c) * ld + r], r < nblk <= ld)
+ * -> the BatchNorm in affine form */
+int eprecon_batchnorm_finalize_affine_async(const float *partial, int64_t nblk, int64_t ld, int channels, const float *gamma,
                                             const float *beta, float eps, float *scale_out, float *shift_out,
                                             void *stream);
 /* out[i, c] = [relu]( x[i, c] * scale[c] + shift[c] ); out may alias x */
@@ -398,11 +402,11 @@ int eprecon_batchnorm_train_async(const float *x, int64_t n, int channels, int l
                                   const float *beta, float eps, const float *residual, int ld_res,
                                   int relu, float *out, int ld_out, float *mean_out, float *var_out,
                                   void *workspace, size_t workspace_bytes, void *stream);
-/* second half of the same BatchNorm from producer-side summaries partial f32[nblk][3][channels]
- * (count, mean, M2 per block, merged in block order) */
+/* second half of the same BatchNorm from producer-side summaries partial f32[3][channels][ld], ld >= nblk
+ * (count, mean, M2 per block, channel-major as eprecon_batchnorm_finalize_affine_async reads them, merged in block order) */
 size_t eprecon_batchnorm_apply_workspace_bytes(int channels);
 int eprecon_batchnorm_apply_partials_async(const float *x, int64_t n, int channels, int ld_x,
-                                           const float *partial, int64_t nblk, const float *gamma,
+                                           const float *partial, int64_t nblk, int64_t ld, const float *gamma,
                                            const float *beta, float eps, const float *residual,
                                            int ld_res, int relu, float *out, int ld_out, float *mean_out,
                                            float *var_out, void *workspace, size_t workspace_bytes,
@@ -410,7 +414,7 @@ int eprecon_batchnorm_apply_partials_async(const float *x, int64_t n, int channe
 /* the same with a residual operand that carries a pending BatchNorm of its own in affine form (the 1x1 skip convolution +
  * BatchNorm of a residual block, models/modules.py:57-65,71): residual' = residual * res_scale + res_shift on load */
 int eprecon_batchnorm_apply_partials_res_async(const float *x, int64_t n, int channels, int ld_x, const float *partial,
-                                               int64_t nblk, const float *gamma, const float *beta, float eps,
+                                               int64_t nblk, int64_t ld, const float *gamma, const float *beta, float eps,
                                                const float *residual, int ld_res, const float *res_scale,
                                                const float *res_shift, int relu, float *out, int ld_out, void *workspace,
                                                size_t workspace_bytes, void *stream);
