@@ -183,9 +183,9 @@ __device__ __forceinline__ void bn_partial_store(const ConvParams &p, int row, i
 // output rows orow[0..3] (-1: no row) x columns 16 t + (l & 15) of its wave's CT accumulator tiles.  Bias, ReLU, residual (with
 // its pending BatchNorm), row-wise LayerNorm (16-lane xor-shuffles), the stores, and the BatchNorm summaries of the workgroup
 // (fixed-order Chan merges: lane groups, then waves) -> bn_partial row `partial_row`, and with ACC also into the accumulator block
-// of BatchNorm form (c) (p.bn_acc).  sStat: >= kWaves * 3 * 16 CT floats of LDS no wave reads any more (the caller's barrier);
-// every thread of the workgroup calls this.
-template <int CT, bool ACC = false>
+// of BatchNorm form (c) (p.bn_acc).  sStat: >= NW * 3 * 16 CT floats of LDS no wave reads any more (the caller's barrier);
+// every thread of the workgroup calls this.  NW: the waves of the workgroup (a wave whose rows are all -1 adds empty summaries).
+template <int CT, bool ACC = false, int NW = kWaves>
 __device__ __forceinline__ void tile16_epilogue(const ConvParams &p, const f32x4 (&acc)[CT], const int (&orow)[4], float *sStat,
                                                 int partial_row)
 {
@@ -281,7 +281,7 @@ __device__ __forceinline__ void tile16_epilogue(const ConvParams &p, const f32x4
         if (tid < 16 * CT && tid < p.Cout) {
             float a_n = 0.0f, a_mean = 0.0f, a_m2 = 0.0f;
 #pragma unroll
-            for (int w = 0; w < kWaves; ++w)
+            for (int w = 0; w < NW; ++w)
                 chan_merge(a_n, a_mean, a_m2, sStat[(w * 3) * 16 * CT + tid], sStat[(w * 3 + 1) * 16 * CT + tid], sStat[(w * 3 + 2) * 16 * CT + tid]);
             if (p.bn_partial) bn_partial_store(p, partial_row, tid, a_n, a_mean, a_m2);
             if (ACC && p.bn_acc) bn_acc_publish(p, tid, partial_row, partial_row == 0, a_n, a_mean, a_m2);
@@ -296,9 +296,20 @@ int launch_direct16(const ConvParams &p, hipStream_t st);
 int direct16_partial_block_rows(const ConvParams &p);   // 128, or 32 when the persistent form takes the launch
 
 // sparse_conv_tile2d.hip: the dense 2D 3x3 layers of the fusion stack on the 16-row image-tile kernel
+// long pixel lists only (the rule dense2d.DIRECT_2D_MIN_ROWS hands the wq16 packing over by); shorter lists: the short-list kernel
+constexpr int kT2MinRows = 40000;
 bool tile2d16_ok(const ConvParams &p);
 int64_t tile2d16_partial_rows(const ConvParams &p);     // one BatchNorm summary row per workgroup (image tile)
 int launch_tile2d16(const ConvParams &p, hipStream_t st);
+
+// sparse_conv_tile2d_short.hip: the 3x3 layers of the 10,800-pixel level (one 16-pixel tile per workgroup, the reduction split
+// across its three waves).  Lists below kT2ShortMaxRows (dense2d.SHORT_2D_MAX_ROWS hands the wq16 packing over by it); between
+// that and kT2MinRows the previous rule holds (split-K, or the direct kernel when the caller packs for it)
+constexpr int kT2ShortMaxRows = 20000;
+bool tile2d_short_list(const ConvParams &p);            // a 3x3 image layer below kT2ShortMaxRows rows
+bool tile2d_short_ok(const ConvParams &p);
+int64_t tile2d_short_partial_rows(const ConvParams &p); // one BatchNorm summary row per workgroup (16-pixel tile)
+int launch_tile2d_short(const ConvParams &p, hipStream_t st);
 
 
 }  // namespace epconv

@@ -2186,8 +2186,15 @@ int conv_dispatch_inner(ConvParams &p, int64_t n_in, hipStream_t st)
         g_last_conv_kernel = "conv2d_tile16_kernel";
         return launch_tile2d16(p, st);
     }
-    // dense 2D 3x3 layers whose caller packed the weights for it: the direct gather kernel on the pixel map
-    const bool direct2d = p.K == 9 && direct16_ok(p);
+    // ... and on short pixel lists: one 16-pixel tile per workgroup, the reduction split across its waves (sparse_conv_tile2d_short.hip;
+    // EPRECON_CONV_TILE2D_SHORT=0: off)
+    if (tile2d_short_ok(p)) {
+        g_last_conv_kernel = "conv2d_tile_short_kernel";
+        return launch_tile2d_short(p, st);
+    }
+    // dense 2D 3x3 layers whose caller packed the weights for it: the direct gather kernel on the pixel map (long lists: the wq16
+    // packing of a short list is the short-list kernel's, which declined)
+    const bool direct2d = p.K == 9 && direct16_ok(p) && !tile2d_short_list(p);
     if (!direct2d) {
         int nt, nch;
         int64_t blocks;
@@ -2220,7 +2227,7 @@ int conv_dispatch_inner(ConvParams &p, int64_t n_in, hipStream_t st)
         g_last_conv_kernel = "spconv_splitk_kernel";
         return vec4 ? launch_splitk_v<true>(p, st) : launch_splitk_v<false>(p, st);
     }
-    if (direct16_ok(p)) {
+    if (direct16_ok(p) && !tile2d_short_list(p)) {
         g_last_conv_kernel = "spconv_direct16_kernel";
         return launch_direct16(p, st);
     }
@@ -2325,14 +2332,14 @@ extern "C" int eprecon_conv_pack_weight_async(const float *weight, int kvol, int
 
 extern "C" size_t eprecon_conv_pack_weight16_floats(int kvol, int cin, int cout)
 {
-    if (kvol <= 0 || cin <= 0 || cout <= 0 || cout > 64) return 0;
+    if (kvol <= 0 || cin <= 0 || cout <= 0 || cout > 80) return 0;
     const int rem = cout - 16 * ((cout + 15) / 16 - 1);      // columns of the last tile: <= 8 -> the tail section follows the tiles
     return (size_t)kvol * ((cin + 15) / 16) * ((cout + 15) / 16) * 256 + (rem <= 8 ? (size_t)kvol * ((cin + 15) / 16) * 128 : 0);
 }
 
 extern "C" int eprecon_conv_pack_weight16_async(const float *weight, int kvol, int cin, int cout, float *packed, void *stream)
 {
-    if (!weight || !packed || kvol <= 0 || cin <= 0 || cout <= 0 || cout > 64) return EPRECON_ERR_ARG;
+    if (!weight || !packed || kvol <= 0 || cin <= 0 || cout <= 0 || cout > 80) return EPRECON_ERR_ARG;
     const size_t total = eprecon_conv_pack_weight16_floats(kvol, cin, cout);
     hipLaunchKernelGGL(pack_weights16_kernel, dim3((unsigned)min((size_t)1024, (total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        weight, kvol, cin, cout, (cin + 15) / 16, (cout + 15) / 16, packed);
@@ -2470,11 +2477,12 @@ extern "C" int64_t eprecon_conv_desc_partial_rows(const eprecon_conv_desc *d)
     if (const int kind = conv3d_kind(p)) return d3_tiles_kind(p, kind);
     p.x_bytes = d->n_in > 0 ? ((d->n_in - 1) * (int64_t)p.ld_x + ((p.Cin + 3) & ~3)) * 4 : 0;
     if (tile2d16_ok(p)) return tile2d16_partial_rows(p);
-    if (p.K == 9 && direct16_ok(p)) return ep::ceil_div(d->n_out, (int64_t)direct16_partial_block_rows(p));
+    if (tile2d_short_ok(p)) return tile2d_short_partial_rows(p);
+    if (p.K == 9 && direct16_ok(p) && !tile2d_short_list(p)) return ep::ceil_div(d->n_out, (int64_t)direct16_partial_block_rows(p));
     if (conv2d_tile_ok(p, &nt, &nch, &blocks)) return blocks;
     if (wide_ok(p)) return ep::ceil_div(d->n_out, (int64_t)kWideRows);
     if (splitk_ok(p)) return ep::ceil_div(d->n_out, (int64_t)32);
-    if (direct16_ok(p)) return ep::ceil_div(d->n_out, (int64_t)direct16_partial_block_rows(p));
+    if (direct16_ok(p) && !tile2d_short_list(p)) return ep::ceil_div(d->n_out, (int64_t)direct16_partial_block_rows(p));
     return ep::ceil_div(d->n_out, (int64_t)kRowsPerBlock);
 }
 

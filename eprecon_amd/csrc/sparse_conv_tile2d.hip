@@ -24,9 +24,7 @@ using namespace ep;
 constexpr int kT2H = 4, kT2W = 16;                                  // tile: image rows x pixels (one row per wave)
 constexpr int kT2HaloW = kT2W + 2, kT2Halo = (kT2H + 2) * kT2HaloW; // 18, 108 pixels
 constexpr int kT2P = 20;                                            // LDS pixel pitch in floats (16 channels + 4)
-// long pixel lists only (the rule dense2d.DIRECT_2D_MIN_ROWS hands the wq16 packing over by): the 10,800-pixel level stays on
-// the split-K kernel
-constexpr int kT2MinRows = 40000;
+// (long pixel lists only: kT2MinRows, conv_common.hpp)
 
 template <int CT, int KCH, bool TAIL8, bool BN>
 __global__ __launch_bounds__(256) void conv2d_tile16_kernel(ConvParams p, int tiles_x, int tiles_per_map)

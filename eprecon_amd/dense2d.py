@@ -82,6 +82,10 @@ def packed_weight(conv):
 # three interleaved pairs); the 10,800-pixel level stays on the split-K kernel (1.459 / 1.494 against 1.448 / 1.467: inside the noise).
 DIRECT_2D_MIN_ROWS = 40000
 K1_DIRECT_2D_MIN_ROWS = 20000     # point-wise layers of the stack (1 x 1 convolutions): see conv_bn_launch
+# 3x3 layers on short pixel lists (the 10,800-pixel level): the short-list image-tile kernel (csrc/sparse_conv_tile2d_short.hip,
+# kT2ShortMaxRows / C_out <= 80); between SHORT_2D_MAX_ROWS and DIRECT_2D_MIN_ROWS the split-K kernel as before
+SHORT_2D_MAX_ROWS = 20000
+SHORT_2D_MAX_COUT = 80
 
 
 # EPRECON_BN_ACC=1: the BatchNorms of the 2D fusion stack finished by their CONSUMERS from order-independent integer accumulators
@@ -227,6 +231,8 @@ def conv_bn_launch(w, bias, gamma, beta, eps, k, x, grid, out=None, aff=None, re
         if n < DIRECT_2D_MIN_ROWS:
             pq = SP.packed_weight(w)                 # short pixel lists (the 10,800-pixel level): B operands of the split-K kernel
             d.packed_weight = pq.data_ptr()
+            if n < SHORT_2D_MAX_ROWS and cout <= SHORT_2D_MAX_COUT:   # ... and of the short-list image-tile kernel (preferred)
+                d.packed_weight16 = SP.packed_weight16(w).data_ptr()
         if cout <= SP.DIRECT_MAX_COUT and n >= DIRECT_2D_MIN_ROWS:
             pw = SP.packed_weight16(w)               # long pixel lists: the direct gather kernel on the pixel map
             d.packed_weight16 = pw.data_ptr()

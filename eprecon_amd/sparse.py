@@ -256,7 +256,7 @@ def packed_weight(weight):
 
 
 def packed_weight16(weight, owner=None):
-    """`weight` f32[K, Cin, Cout <= 64] in the operand order of the 16x16x4 MFMA kernels (16-row tile kernel, direct gather
+    """`weight` f32[K, Cin, Cout <= 80] in the operand order of the 16x16x4 MFMA kernels (16-row tile kernel, direct gather
     kernel), packed once per weight version.  owner: the tensor OBJECT the packing is cached on when `weight` is a transient
     view of it (a [Cin, Cout] matrix unsqueezed to K = 1)"""
     owner = weight if owner is None else owner
