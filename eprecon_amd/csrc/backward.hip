@@ -294,13 +294,14 @@ int eprecon_sparse_conv_wgrad_async(const float *x, int ld_x, const float *dy, i
                                     int64_t n_out, int cin, int cout, float *dweight, void *workspace,
                                     size_t workspace_bytes, void *stream)
 {
-    if (!x || !dy || !dweight || kvol < 1 || cin < 1 || cout < 1 || n_out < 0 || (!nbr && kvol != 1)) return EPRECON_ERR_ARG;
+    if (!dweight || kvol < 1 || cin < 1 || cout < 1 || n_out < 0) return EPRECON_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int64_t elems = (int64_t)kvol * cin * cout;
-    if (n_out == 0) {
+    if (n_out == 0) {   // (before the operand checks: the rows and the map of an empty list have no storage, their pointers are null)
         EP_HIP_CHECK(hipMemsetAsync(dweight, 0, elems * sizeof(float), st));
         return EPRECON_OK;
     }
+    if (!x || !dy || (!nbr && kvol != 1)) return EPRECON_ERR_ARG;
     if (workspace_bytes < eprecon_sparse_conv_wgrad_workspace_bytes(kvol, n_out, cin, cout) || !workspace)
         return EPRECON_ERR_WORKSPACE;
     int ti, tj;
