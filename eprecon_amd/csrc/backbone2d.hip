@@ -4,7 +4,8 @@
 // naive reference kernel (1.85 of the 4.4 ms of a 9-view pass, profiles/r04/backbone_kernels.txt) and PyTorch's instance-norm
 // route costs four launches per BatchNorm; the point-wise (1 x 1) layers are plain GEMMs and stay on hipBLASLt.
 //
-//   bn_views_stats_kernel   a view's rows are cut into `chunks` ranges, one workgroup each: shifted sums -> (n, mean, M2) per channel
+//   bn_views_stats_kernel   a view's rows are cut into `chunks` ranges, one workgroup each: (n, mean, M2) per channel and lane
+//                           (two-pass over four rows at a time, Chan merges), the lanes merged in order
 //   bn_views_finalize_kernel  the range summaries of a view merged in range order (Chan) -> the BatchNorm as
 //                           scale = g / sqrt(var + eps), shift = b - mean * scale per (view, channel).  Deterministic.
 //   bn_views_apply_kernel   y = [relu](x * scale + shift) [+ residual]   (in place or not)
@@ -27,53 +28,69 @@ struct BnViewsParams {
     float *affine;           // [V][2][C]
 };
 
+// (n, mean, M2) += a summary of n_b rows (mean_b, m2_b), per component: Chan et al.'s pairwise update
+__device__ __forceinline__ void chan_merge4(float &n, float4 &mean, float4 &m2, float n_b, float4 mean_b, float4 m2_b)
+{
+    const float nn = n + n_b, wb = n_b / nn, wq = n * n_b / nn;
+    const float dx = mean_b.x - mean.x, dy = mean_b.y - mean.y, dz = mean_b.z - mean.z, dw = mean_b.w - mean.w;
+    mean.x += dx * wb; mean.y += dy * wb; mean.z += dz * wb; mean.w += dw * wb;
+    m2.x += m2_b.x + dx * dx * wq; m2.y += m2_b.y + dy * dy * wq; m2.z += m2_b.z + dz * dz * wq; m2.w += m2_b.w + dw * dw * wq;
+    n = nn;
+}
+
 __global__ __launch_bounds__(256) void bn_views_stats_kernel(BnViewsParams p)
 {
-    __shared__ float sS[1024], sQ[1024];
+    __shared__ float sN[256], sM[1024], sQ[1024];
     const int tid = threadIdx.x, view = blockIdx.y, chunk = blockIdx.x;
     const int C = p.C, C4 = C >> 2, R = 256 / C4;
     const int c4 = tid % C4, r = tid / C4;
     const int per = (p.rows_per_view + p.chunks - 1) / p.chunks;
     const int r0 = chunk * per, r1 = min(p.rows_per_view, r0 + per);
     const float *base = p.x + (size_t)view * p.rows_per_view * C;
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f), q = s, pv = s;
+    // a lane's rows as a running (n, mean, M2): every four rows two-pass around their own mean, then merged.  (Sums shifted by
+    // one pivot row lose the variance to cancellation when that row lies far from the others: a single outlier did.)
+    float n = 0.0f;
+    float4 mean = make_float4(0.f, 0.f, 0.f, 0.f), m2 = mean;
     if (r < R && r0 < r1) {
-        pv = *reinterpret_cast<const float4 *>(base + (size_t)r0 * C + 4 * c4);     // pivot: the sums run on x - pivot
-        // four rows in flight per thread (independent loads, one accumulator pair: the adds are cheap, the latency is not)
+        // four rows in flight per thread (independent loads: the latency, not the arithmetic, is what the loop costs)
         int row = r0 + r;
         for (; row + 3 * R < r1; row += 4 * R) {
             float4 v[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float4 *>(base + (size_t)(row + u * R) * C + 4 * c4);
+            const float4 m4 = make_float4((v[0].x + v[1].x + v[2].x + v[3].x) * 0.25f, (v[0].y + v[1].y + v[2].y + v[3].y) * 0.25f,
+                                          (v[0].z + v[1].z + v[2].z + v[3].z) * 0.25f, (v[0].w + v[1].w + v[2].w + v[3].w) * 0.25f);
+            float4 q4 = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const float dx = v[u].x - pv.x, dy = v[u].y - pv.y, dz = v[u].z - pv.z, dw = v[u].w - pv.w;
-                s.x += dx; s.y += dy; s.z += dz; s.w += dw;
-                q.x = fmaf(dx, dx, q.x); q.y = fmaf(dy, dy, q.y); q.z = fmaf(dz, dz, q.z); q.w = fmaf(dw, dw, q.w);
+                const float dx = v[u].x - m4.x, dy = v[u].y - m4.y, dz = v[u].z - m4.z, dw = v[u].w - m4.w;
+                q4.x = fmaf(dx, dx, q4.x); q4.y = fmaf(dy, dy, q4.y); q4.z = fmaf(dz, dz, q4.z); q4.w = fmaf(dw, dw, q4.w);
             }
+            chan_merge4(n, mean, m2, 4.0f, m4, q4);
         }
-        for (; row < r1; row += R) {
-            const float4 v = *reinterpret_cast<const float4 *>(base + (size_t)row * C + 4 * c4);
-            const float dx = v.x - pv.x, dy = v.y - pv.y, dz = v.z - pv.z, dw = v.w - pv.w;
-            s.x += dx; s.y += dy; s.z += dz; s.w += dw;
-            q.x = fmaf(dx, dx, q.x); q.y = fmaf(dy, dy, q.y); q.z = fmaf(dz, dz, q.z); q.w = fmaf(dw, dw, q.w);
-        }
+        for (; row < r1; row += R)
+            chan_merge4(n, mean, m2, 1.0f, *reinterpret_cast<const float4 *>(base + (size_t)row * C + 4 * c4), make_float4(0.f, 0.f, 0.f, 0.f));
     }
     if (r < R) {
-        *reinterpret_cast<float4 *>(sS + r * C + 4 * c4) = s;
-        *reinterpret_cast<float4 *>(sQ + r * C + 4 * c4) = q;
+        if (c4 == 0) sN[r] = n;
+        *reinterpret_cast<float4 *>(sM + r * C + 4 * c4) = mean;
+        *reinterpret_cast<float4 *>(sQ + r * C + 4 * c4) = m2;
     }
     __syncthreads();
     float *dst = p.partial + ((size_t)view * p.chunks + chunk) * 3 * C;
     for (int c = tid; c < C; c += 256) {
-        float ts = 0.0f, tq = 0.0f;
-        for (int k = 0; k < R; ++k) { ts += sS[k * C + c]; tq += sQ[k * C + c]; }
-        const float n = (float)max(r1 - r0, 0);
-        const float pivot = r0 < r1 ? base[(size_t)r0 * C + c] : 0.0f;
-        const float dm = n > 0.0f ? ts / n : 0.0f;
-        dst[c] = n;
-        dst[C + c] = pivot + dm;
-        dst[2 * C + c] = fmaxf(tq - ts * dm, 0.0f);
+        float tn = 0.0f, tm = 0.0f, tq = 0.0f;      // the R lanes merged in lane order
+        for (int k = 0; k < R; ++k) {
+            const float nb = sN[k];
+            if (nb <= 0.0f) continue;
+            const float nn = tn + nb, d = sM[k * C + c] - tm;
+            tm += d * (nb / nn);
+            tq += sQ[k * C + c] + d * d * (tn * nb / nn);
+            tn = nn;
+        }
+        dst[c] = tn;
+        dst[C + c] = tm;
+        dst[2 * C + c] = tq;
     }
 }
 

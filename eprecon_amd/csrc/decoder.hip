@@ -282,7 +282,7 @@ __global__ __launch_bounds__(64) void masked_attention_reduce_kernel(const float
 // fp32 round-off.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int kQsRows = 2;        // query rows per workgroup
-constexpr int kQsThreads = 384;   // >= the widest layer (ffn_dim, mask_hidden); the narrow layers split their sum over 384 / N parts
+constexpr int kQsThreads = 384;   // >= the widest layer (3 C, kQsMaxW); the narrow layers split their sum over 384 / N parts
 constexpr int kQsMaxC = 64;       // channels (one wave holds a row for the LayerNorms)
 
 // y[r][n] = [relu]( bias[n] + sum_k x[r][k] * wt[k][n] ) for the workgroup's rows; x / y in LDS (row pitch ldx / ldy), wt [K][N]
@@ -402,7 +402,7 @@ __global__ __launch_bounds__(kQsThreads) void query_side_a_kernel(QsParams p)
 }
 
 constexpr int kQsMaxQ = 128;      // queries (the self-attention's key axis, held in LDS per head)
-constexpr int kQsMaxW = 256;      // widest hidden layer
+constexpr int kQsMaxW = 256;      // widest hidden layer (ffn_dim, mask_hidden): the row pitch of sH1 / sH2; the guard refuses wider
 __global__ __launch_bounds__(kQsThreads) void query_side_b_kernel(QsParams p)
 {
     __shared__ float sT1[kQsRows * kQsMaxC], sA[kQsRows * kQsMaxC], sU[kQsRows * kQsMaxC], sT2[kQsRows * kQsMaxC];
@@ -583,8 +583,8 @@ int eprecon_decoder_query_side_async(const eprecon_decoder_layer_desc *d, void *
         !d->m3_wt || !d->m3_b || (d->next_q_wt && (!d->next_q_b || !d->next_q_out)))
         return EPRECON_ERR_ARG;
     const int Q = d->n_queries, C = d->channels, H = d->n_heads;
-    if (Q <= 0 || Q > kQsMaxQ || C <= 0 || C > kQsMaxC || H <= 0 || H > 8 || C % H || d->ffn_dim <= 0 || d->ffn_dim > kQsThreads ||
-        d->mask_hidden <= 0 || d->mask_hidden > kQsThreads || d->n_class_logits <= 0 || d->n_class_logits > kQsMaxC || 3 * C > kQsThreads)
+    if (Q <= 0 || Q > kQsMaxQ || C <= 0 || C > kQsMaxC || H <= 0 || H > 8 || C % H || d->ffn_dim <= 0 || d->ffn_dim > kQsMaxW ||
+        d->mask_hidden <= 0 || d->mask_hidden > kQsMaxW || d->n_class_logits <= 0 || d->n_class_logits > kQsMaxC || 3 * C > kQsThreads)
         return EPRECON_ERR_UNSUPPORTED;
     QsParams p;
     p.Q = Q; p.C = C; p.H = H; p.FF = d->ffn_dim; p.K1 = d->n_class_logits; p.MH = d->mask_hidden;

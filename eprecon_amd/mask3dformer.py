@@ -454,7 +454,7 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
             c = self.query_feat.weight.shape[1]
             ffn = self.transformer_ffn_layers[0].linear1.out_features
             if (c // self.num_heads == 6 and self.num_heads % 2 == 0 and self.num_heads <= 8 and c <= 64 and self.num_queries <= 128
-                    and ffn <= 192 and self.mask_embed.layers[0].out_features <= 192 and self._query_side_pack(mask_features.device)["ok"]):
+                    and ffn <= 256 and self.mask_embed.layers[0].out_features <= 256 and self._query_side_pack(mask_features.device)["ok"]):
                 return self._forward_fused(panoptic_features, panoptic_coords, mask_features, spitial_shape)
         pos = self.get_pos_encs(panoptic_coords, spitial_shape)
         src, sizes = [], []

@@ -844,7 +844,7 @@ int eprecon_masked_attention_async(const float *q, int q_stride_head, int q_stri
  * in-projected queries — two launches instead of ~25.  Every weight matrix is given TRANSPOSED, f32[in][out] row-major
  * (nn.Linear stores [out][in]); self_in_wt is nn.MultiheadAttention.in_proj_weight transposed: f32[C][3C] with the q | k | v
  * columns side by side.  workspace: 4 * Q * C floats.  Shapes taken: Q <= 128, C <= 64 with C % H == 0, H <= 8,
- * ffn_dim / mask_hidden <= 192, n_class_logits <= 64 (EPRECON_ERR_UNSUPPORTED otherwise).
+ * ffn_dim / mask_hidden <= 256, n_class_logits <= 64 (EPRECON_ERR_UNSUPPORTED otherwise).
  */
 typedef struct eprecon_decoder_layer_desc {
     int n_queries; int channels; int n_heads; int ffn_dim; int n_class_logits; int mask_hidden;
