@@ -7,6 +7,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/eprecon_hip.h"
 
@@ -24,6 +25,13 @@ constexpr int kXcd = 8;
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// an on/off environment switch that defaults to on: NAME=0 turns it off.  Read at every call: tests flip the switches.
+inline bool switch_off(const char *name)
+{
+    const char *e = getenv(name);
+    return e && e[0] == '0';
+}
 
 // Hardware block id -> logical block id.  The dispatcher places hardware block h on XCD h % 8
 // (observed, speed only); this bijection gives every XCD one contiguous range of logical blocks

@@ -1,5 +1,7 @@
-// Shared between the translation units of the convolution family (sparse_conv.hip, sparse_conv_direct.hip): the launch
-// parameters, the Chan merge of BatchNorm summaries and the entry points of the direct gather kernel.
+// Shared between the translation units of the convolution family (the dispatcher sparse_conv.hip and one sparse_conv_*.hip per
+// kernel family): the launch parameters, the BatchNorm summary helpers, the epilogue of the 16-row tile kernels, and at the end
+// each family's contract with the dispatcher: its eligibility rule, the BatchNorm summary rows (or the rows of a summary block)
+// of its launch, and its launcher, which picks the template instantiation.
 #pragma once
 #include "common.hpp"
 
@@ -151,6 +153,8 @@ __device__ __forceinline__ void bn_acc_publish(const ConvParams &p, int col, int
 }
 
 constexpr int kWaves = 4;
+constexpr int kRowsPerWave = 32;
+constexpr int kRowsPerBlock = kRowsPerWave * kWaves;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
@@ -288,6 +292,45 @@ __device__ __forceinline__ void tile16_epilogue(const ConvParams &p, const f32x4
         }
     }
 }
+
+// 16-byte gathers need aligned rows; a channel count that is not a multiple of 4 is fine as long as the
+// row pitch covers the rounded-up count (the tail lanes are zeroed after the load)
+inline bool gather_vec4(const ConvParams &p)
+{
+    return (p.ld_x % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.x) & 15) == 0) && (p.Cin % 4 == 0 || p.ld_x >= ((p.Cin + 3) & ~3));
+}
+
+// sparse_conv_dense3d.hip: the 3x3x3 stride-1 convolution on a dense grid (vox_rank), no kernel map
+enum D3Kind { kD3None = 0, kD3Narrow = 1, kD3Tile16 = 2 };
+int conv3d_kind(const ConvParams &p);                   // which of the two kernels takes the layer (EPRECON_CONV_DENSE3D)
+int d3_tiles_kind(const ConvParams &p, int kind, int *ty = nullptr, int *tz = nullptr);   // workgroups = BatchNorm summary rows
+int launch_conv3d_16(const ConvParams &p, hipStream_t st);
+int launch_conv3d_single_column(const ConvParams &p, hipStream_t st);
+
+// sparse_conv_slab.hip: dense 2D 3x3 layers with C_in <= 40 on 8 x 16 pixel tiles (conv2d_tile_kernel)
+// eligibility of the tile kernel; on success *blocks = workgroups per column block (= BatchNorm summary rows)
+bool conv2d_tile_ok(const ConvParams &p, int *nt_out, int *nch_out, int64_t *blocks);
+int launch_image_tile(const ConvParams &p, hipStream_t st);
+
+// sparse_conv_wide.hip: medium lists with wide channels, the offsets split across workgroups (needs the caller's workspace)
+constexpr int kWideRows = 128;
+size_t wide_workspace_bytes(const ConvParams &p);
+bool wide_shape_ok(const ConvParams &p);                // shape / alignment rule, independent of the workspace
+bool wide_ok(const ConvParams &p);
+int launch_wide(const ConvParams &p, hipStream_t st);
+
+// sparse_conv_splitk.hip: short lists; one BatchNorm summary row per 32-row tile
+constexpr int kSplitKRows = 32;
+bool splitk_ok(const ConvParams &p);
+int launch_splitk(ConvParams &p, hipStream_t st);       // (sets p.splitk_pipe)
+
+// sparse_conv_slab.hip, sparse_conv_resident_nt{1,2}.hip: the gather kernels with 128-row (kRowsPerBlock) workgroups; the slab
+// kernel takes whatever is left
+bool resident_narrow_ok(const ConvParams &p);
+int launch_resident_narrow(const ConvParams &p, hipStream_t st);
+bool resident_wide_ok(const ConvParams &p);
+int launch_resident_wide(const ConvParams &p, hipStream_t st);
+int launch_mfma(const ConvParams &p, hipStream_t st);
 
 // sparse_conv_direct.hip: the long-list 3x3x3 kernel on 16x16x4 MFMAs with operands straight from L2
 bool direct16_ok(const ConvParams &p);

@@ -11,8 +11,7 @@ int launch_direct16_ct4(const ConvParams &p, hipStream_t st);
 // EPRECON_CONV_DIRECT=0: the LDS-resident kernels for every long list (read per launch: tests flip it)
 bool direct16_ok(const ConvParams &p)
 {
-    const char *e = getenv("EPRECON_CONV_DIRECT");
-    if (e && e[0] == '0') return false;
+    if (switch_off("EPRECON_CONV_DIRECT")) return false;
     // 3x3x3 kernel maps, the 3x3 pixel maps of the dense 2D stack, and point-wise layers on long lists (K = 1, identity map: a
     // streaming [N, C_in] x [C_in, C_out] product) — the caller packs the weights only where it wants this kernel
     const bool pointwise = p.K == 1 && !p.nbr;

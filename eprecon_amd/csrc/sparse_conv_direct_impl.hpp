@@ -1034,8 +1034,7 @@ __global__ __launch_bounds__(256) void spconv_direct16_generic_kernel(ConvParams
 // EPRECON_CONV_TAIL8=0: C_out = 16 m + 8 on padded 16-column tiles (the round-5 form; read per launch: tests flip it)
 static bool tail8_enabled()
 {
-    const char *e = getenv("EPRECON_CONV_TAIL8");
-    return !(e && e[0] == '0');
+    return !switch_off("EPRECON_CONV_TAIL8");
 }
 
 // EPRECON_CONV_BF16X3=1: the template kernel's bf16x3 operand form (C_in <= 96, C_out <= 64; read per launch).  OFF by default:
@@ -1050,15 +1049,13 @@ static bool bf16x3_enabled()
 // kernel (read per launch); default: branch-free layers spread the loads among the MFMAs.  Same arithmetic in the same order.
 static bool interleave_enabled()
 {
-    const char *e = getenv("EPRECON_CONV_INTERLEAVE");
-    return !(e && e[0] == '0');
+    return !switch_off("EPRECON_CONV_INTERLEAVE");
 }
 
 // EPRECON_CONV_STAGE_DEPTH=0: always the deepest prefetch stage (the round-5 rule; read per launch)
 static bool stage_depth_enabled()
 {
-    const char *e = getenv("EPRECON_CONV_STAGE_DEPTH");
-    return !(e && e[0] == '0');
+    return !switch_off("EPRECON_CONV_STAGE_DEPTH");
 }
 
 constexpr size_t kLdsBytes = 160 * 1024;

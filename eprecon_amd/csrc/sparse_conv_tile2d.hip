@@ -1,5 +1,5 @@
 // Dense 2D 3x3 'same' convolution on v_mfma_f32_16x16x4_f32 over the [V * H * W, C] pixel rows of the 2D fusion stack: the 2D
-// twin of conv3d_tile16_kernel (sparse_conv.hip).  The direct gather kernel runs these layers through the pixel map: nine index
+// twin of conv3d_tile16_kernel (sparse_conv_dense3d.hip).  The direct gather kernel runs these layers through the pixel map: nine index
 // loads per row, each followed by a dependent 16-byte gather, and every input row read nine times through L1 (a 12 -> 12 layer
 // on 172,800 pixels took 27-38 us for 8 us of padded MFMA work and 4 us of streaming).  Here the input is read once per tile:
 //   - a workgroup owns 4 image rows x 16 pixels of one view; wave w owns row w (one 16-row MFMA tile) and all CT column tiles
@@ -205,8 +205,7 @@ int launch_t2_kch(const ConvParams &p, hipStream_t st)
 // PRODUCER side of form (c) (bn_acc) is taken: a layer's rows are the same bits under either BatchNorm form.
 bool tile2d16_ok(const ConvParams &p)
 {
-    const char *e = getenv("EPRECON_CONV_TILE2D16");
-    if (e && e[0] == '0') return false;
+    if (switch_off("EPRECON_CONV_TILE2D16")) return false;
     if (p.K != 9 || p.img_h <= 0 || p.img_w <= 0 || p.img_maps <= 0 || (int64_t)p.img_maps * p.img_h * p.img_w != p.n_out)
         return false;
     if (p.n_out < kT2MinRows || p.ln || p.accumulate || p.in_acc) return false;

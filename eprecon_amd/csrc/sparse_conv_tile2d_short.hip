@@ -210,8 +210,7 @@ bool tile2d_short_list(const ConvParams &p) { return p.K == 9 && p.img_maps > 0 
 // accumulate, unaligned inputs or weights.
 bool tile2d_short_ok(const ConvParams &p)
 {
-    const char *e = getenv("EPRECON_CONV_TILE2D_SHORT");
-    if (e && e[0] == '0') return false;
+    if (switch_off("EPRECON_CONV_TILE2D_SHORT")) return false;
     if (!tile2d_short_list(p) || p.img_h <= 0 || p.img_w <= 0 || (int64_t)p.img_maps * p.img_h * p.img_w != p.n_out) return false;
     if (p.ln || p.accumulate || p.in_acc) return false;
     const int ct = (p.Cout + 15) / 16, kch = (p.Cin + 15) / 16;

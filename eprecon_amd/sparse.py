@@ -16,7 +16,7 @@ import os
 
 def _dense3d_level():
     """EPRECON_CONV_DENSE3D: 0 off, 1 the single-column (C_out == 1) kernel only, 2 (default) also the 16-row MFMA tile kernel
-    (C_out <= 32, C_in % 16 == 0); csrc/sparse_conv.hip, conv3d_kind"""
+    (C_out <= 32, C_in % 16 == 0); csrc/sparse_conv_dense3d.hip, conv3d_kind"""
     return int(os.environ.get("EPRECON_CONV_DENSE3D", "2"))
 
 
@@ -163,7 +163,7 @@ class DenseMap:
         return int(self.rank[-1].item())
 
     def kind(self, x, cin, cout, accumulate=False, ln=False, stats=False):
-        """mirror of the library's rule (conv3d_kind, csrc/sparse_conv.hip): 0 none (kernel map), 1 single-column kernel,
+        """mirror of the library's rule (conv3d_kind, csrc/sparse_conv_dense3d.hip): 0 none (kernel map), 1 single-column kernel,
         2 16-row MFMA kernel"""
         level = _dense3d_level()
         if level <= 0 or cin % 4 or cin > 64 or x.stride(0) % 4 or x.data_ptr() % 16:
@@ -377,7 +377,7 @@ def _resolve_map(nbr, x, weight, desc, accumulate=False, ln=False, stats=False, 
         keep.append(pw)
     if nbr is not None and weight.shape[0] == 27 and weight.shape[2] <= DIRECT_MAX_COUT \
             and not accumulate and x.is_cuda:
-        # long lists: the direct gather kernel takes its B operands pre-packed (csrc/sparse_conv.hip, spconv_direct16_kernel);
+        # long lists: the direct gather kernel takes its B operands pre-packed (csrc/sparse_conv_direct_impl.hpp, spconv_direct16_kernel);
         # which kernel runs is the library's choice, the packing only makes the direct one possible
         pw = packed_weight16(weight)
         desc.packed_weight16 = pw.data_ptr()

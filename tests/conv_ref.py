@@ -1,4 +1,4 @@
-"""Float64 reference of the convolution family (csrc/sparse_conv.hip and the kernels it dispatches to), in plain torch.
+"""Float64 reference of the convolution family (csrc/sparse_conv.hip and the family units csrc/sparse_conv_*.hip it dispatches to), in plain torch.
 
 Independent of oracle/: every function works on torch tensors (on the GPU when the operands are there, so the references of
 long lists stay cheap) and computes in float64.  Each result comes with S = sum |a| |w| + |b| + |residual| (+ |out| for

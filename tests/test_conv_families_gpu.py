@@ -1,4 +1,4 @@
-"""Conformance of every kernel family of the convolution dispatcher (conv_dispatch_inner, csrc/sparse_conv.hip) against the
+"""Conformance of every kernel family of the convolution dispatcher (select_conv, csrc/sparse_conv.hip) against the
 float64 reference of tests/conv_ref.py.
 
 FAMILIES maps each name the dispatcher can report (_lib.last_conv_kernel) to the cases built to reach it, each with the
@@ -205,8 +205,9 @@ CASES = [pytest.param(fam, c, id=f"{fam}-{c['id']}") for fam, cs in FAMILIES.ite
 def test_table_names_exactly_the_dispatched_families():
     """CPU: the names the dispatcher can report are exactly the table's keys (a family added or removed fails here)"""
     with open(os.path.join(ROOT, "eprecon_amd", "csrc", "sparse_conv.hip")) as f:
-        names = {s for line in f if re.search(r"\bg_last_conv_kernel\s*=", line) for s in re.findall(r'"([^"]*)"', line)}
-    names.discard("")
+        table = re.search(r"\bkConvFamilyNames\[\]\s*=\s*\{(.*?)\};", f.read(), re.S)     # the dispatcher's one table of names
+    assert table
+    names = set(re.findall(r'"([^"]*)"', table.group(1)))
     assert names == set(FAMILIES), (sorted(names - set(FAMILIES)), sorted(set(FAMILIES) - names))
     for fam, cs in FAMILIES.items():
         assert cs, fam

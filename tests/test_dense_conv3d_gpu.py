@@ -1,4 +1,4 @@
-"""Dense-grid forms of the 3x3x3 stride-1 convolution (conv3d_tile16_kernel / conv3d_tile_narrow_kernel, csrc/sparse_conv.hip)
+"""Dense-grid forms of the 3x3x3 stride-1 convolution (conv3d_tile16_kernel / conv3d_tile_narrow_kernel, csrc/sparse_conv_dense3d.hip)
 against (a) the gather-GEMM form of the same layer through the [27, N] kernel map — equal within fp32 round-off: the tile
 kernels multiply four input channels per MFMA, another summation order — and (b) the numpy oracle (oracle/sparse.py, restating
 the spconv SubMConv3d semantics of models/modules.py:249-271) within 1e-3."""

@@ -95,3 +95,99 @@ def test_backbone_walker_on_the_pytorch_fallbacks():
             assert a.shape == b.shape
             assert torch.allclose(a, b, rtol=1e-4, atol=1e-4), float((a - b).abs().max())
             x = a
+
+
+def _conv_desc(n_out, kvol, cin, cout, **kw):
+    """a ConvDesc with made-up 16-byte aligned addresses: the two sizing entry points below are host arithmetic and
+    dereference nothing.  Rows of cin / cout floats, as many input rows as output rows, a kernel map unless nbr=0 is given."""
+    from eprecon_amd import _lib
+    d = _lib.ConvDesc()
+    d.x, d.n_in, d.ld_x = 0x10000, n_out, cin
+    d.nbr, d.kvol, d.n_out = 0x20000, kvol, n_out
+    d.weight, d.cin, d.cout = 0x30000, cin, cout
+    d.out, d.ld_out = 0x40000, cout
+    for k, v in kw.items():
+        setattr(d, k, v)
+    return d
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def test_summary_rows_and_workspace_per_convolution_family(monkeypatch):
+    """eprecon_conv_desc_partial_rows / eprecon_conv_desc_workspace_bytes against each family's documented workgroup, at the
+    smallest shapes on either side of a selection boundary (the direct gather kernel is left out: its block rows depend on the
+    device, so the shapes that would reach it run with EPRECON_CONV_DIRECT=0)"""
+    import ctypes
+    import os
+    from eprecon_amd import _lib
+    lib = _lib.load()
+    for name in [k for k in os.environ if k.startswith("EPRECON_CONV_") or k == "EPRECON_BN_ACC"]:
+        monkeypatch.delenv(name)
+
+    def rows(d):
+        return lib.eprecon_conv_desc_partial_rows(ctypes.byref(d))
+
+    def ws(d):
+        return lib.eprecon_conv_desc_workspace_bytes(ctypes.byref(d))
+
+    PACK, PACK16, RANK = 0x50000, 0x60000, 0x70000
+    # ---- gather forms on a kernel map: 128-row workgroups (resident, resident on wide inputs, the slab kernel) ----
+    for kvol, cin, cout, n in [(27, 32, 32, 100000), (27, 64, 64, 40000), (27, 72, 64, 40000), (9, 72, 64, 40001), (27, 20, 130, 33333)]:
+        d = _conv_desc(n, kvol, cin, cout)
+        assert rows(d) == _cdiv(n, 128) and ws(d) == 0, (kvol, cin, cout, n)
+    # ---- split-K: 32-row summary blocks while the 128-row blocks x column tiles number 256 at most ----
+    assert rows(_conv_desc(256 * 128, 27, 32, 32)) == 256 * 4
+    assert rows(_conv_desc(256 * 128 + 1, 27, 32, 32)) == 257                      # one block more: resident
+    assert rows(_conv_desc(128 * 128, 27, 72, 64)) == 128 * 4                      # two column tiles: 256 blocks
+    assert rows(_conv_desc(128 * 128 + 1, 27, 72, 64)) == 129
+    assert rows(_conv_desc(1000, 27, 32, 32, accumulate=1)) == 8                   # accumulate: never split-K
+    monkeypatch.setenv("EPRECON_CONV_SPLITK", "0")
+    assert rows(_conv_desc(1000, 27, 32, 32)) == 8
+    monkeypatch.delenv("EPRECON_CONV_SPLITK")
+    # ---- wide (cross-workgroup split of the offsets): 4,096..40,000 rows, C_in >= 96, 64 < C_out <= 128, packed weights, and
+    # only with the workspace the library asks for; otherwise the shape is split-K's ----
+    for n, cin, cout, wide in [(4096, 96, 65, True), (4095, 96, 65, False), (4096, 96, 64, False), (4096, 92, 65, False),
+                               (40000, 128, 128, True), (40001, 128, 128, False), (4096, 96, 129, False)]:
+        d = _conv_desc(n, 27, cin, cout, packed_weight=PACK)
+        need = ws(d)
+        assert (need > 0) == wide, (n, cin, cout)
+        short = _cdiv(n, 128) * _cdiv(cout, 32) <= 256
+        other = _cdiv(n, 32) if short else _cdiv(n, 128)
+        assert rows(d) == other, (n, cin, cout)                                    # no workspace given
+        if wide:
+            d.workspace, d.workspace_bytes = 0x80000, need
+            assert rows(d) == _cdiv(n, 128), (n, cin, cout)
+            d.workspace_bytes = need - 1
+            assert rows(d) == other, (n, cin, cout)
+    assert ws(_conv_desc(4096, 27, 96, 65)) == 0                                   # no packed weights: not wide
+    monkeypatch.setenv("EPRECON_CONV_WIDEK", "0")
+    assert ws(_conv_desc(4096, 27, 96, 65, packed_weight=PACK)) == 0
+    monkeypatch.delenv("EPRECON_CONV_WIDEK")
+    # ---- conv2d_tile: 8 x 16 pixel tiles, from 256 tiles on ----
+    img = dict(img_h=30, img_w=40)                                                 # 4 x 3 tiles per map, neither edge a multiple
+    assert rows(_conv_desc(22 * 1200, 9, 24, 24, img_maps=22, **img)) == 22 * 12
+    assert rows(_conv_desc(21 * 1200, 9, 24, 24, img_maps=21, **img)) == _cdiv(21 * 1200, 32)     # 252 tiles: split-K
+    assert rows(_conv_desc(30 * 1200, 9, 44, 24, img_maps=30, **img)) == _cdiv(30 * 1200, 128)    # six 8-channel chunks: resident
+    # ---- the 16-row image-tile kernel: 4 x 16 pixel tiles, lists of kT2MinRows = 40,000 rows and more, wq16 packing ----
+    monkeypatch.setenv("EPRECON_CONV_DIRECT", "0")
+    assert rows(_conv_desc(40000, 9, 24, 24, img_maps=1, img_h=200, img_w=200, packed_weight16=PACK16)) == 50 * 13
+    assert rows(_conv_desc(39999, 9, 24, 24, img_maps=1, img_h=199, img_w=201, packed_weight16=PACK16)) == 25 * 13   # conv2d_tile
+    assert rows(_conv_desc(40000, 9, 52, 24, img_maps=1, img_h=200, img_w=200, packed_weight16=PACK16)) == _cdiv(40000, 128)
+    # ---- the short-list image kernel: one 16-pixel segment of a row per workgroup, lists below kT2ShortMaxRows = 20,000 ----
+    assert rows(_conv_desc(10800, 9, 80, 40, img_maps=9, img_h=30, img_w=40, packed_weight16=PACK16)) == 9 * 30 * 3
+    assert rows(_conv_desc(19999, 9, 80, 40, img_maps=1, img_h=2857, img_w=7, packed_weight16=PACK16)) == 2857
+    assert rows(_conv_desc(20006, 9, 80, 40, img_maps=1, img_h=2858, img_w=7, packed_weight16=PACK16)) == _cdiv(20006, 128)
+    assert rows(_conv_desc(10800, 9, 80, 40, img_maps=9, img_h=30, img_w=40)) == _cdiv(10800, 32)   # no packing: split-K
+    # ---- dense-grid 3D: tiles of 4 x 4 x 8 cells (single column) or 2 x 4 x 8 (16-row MFMA kernel) over the whole grid ----
+    grid = dict(vox_rank=RANK, grid_x=9, grid_y=10, grid_z=11)
+    assert rows(_conv_desc(700, 27, 32, 1, **grid)) == 3 * 3 * 2
+    assert rows(_conv_desc(700, 27, 32, 16, packed_weight16=PACK16, **grid)) == 5 * 3 * 2
+    assert rows(_conv_desc(700, 27, 32, 16, **grid)) == _cdiv(700, 32)             # no packing: the kernel map (split-K)
+    monkeypatch.setenv("EPRECON_CONV_DENSE3D", "1")
+    assert rows(_conv_desc(700, 27, 32, 1, **grid)) == 18
+    assert rows(_conv_desc(700, 27, 32, 16, packed_weight16=PACK16, **grid)) == _cdiv(700, 32)
+    monkeypatch.setenv("EPRECON_CONV_DENSE3D", "0")
+    assert rows(_conv_desc(700, 27, 32, 1, **grid)) == _cdiv(700, 32)
+    assert rows(_conv_desc(0, 27, 32, 32)) == 0 and ws(_conv_desc(0, 27, 96, 65, packed_weight=PACK)) == 0
