@@ -119,6 +119,7 @@ SIGNATURES = {
     "eprecon_map_target_fuse": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i64, _vp, _vp]),
     "eprecon_gather_rows_async": (_i, [_vp, _i, _vp, _i64, _i, _f, _vp, _i, _vp]),
     "eprecon_tsdf_integrate_async": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _vp, _vp, _f, _f, _i, _vp, _vp]),
+    "eprecon_gt_crop_async": (_i, [_vp, _vp]),
     "eprecon_marching_cubes_table": (_i, [_vp]),
     "eprecon_marching_cubes_workspace_bytes": (_sz, [_i, _i, _i]),
     "eprecon_marching_cubes_count": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),
@@ -242,6 +243,15 @@ class ViewsDesc(ctypes.Structure):
     """include/eprecon_hip.h: eprecon_views_desc"""
     _fields_ = [("src", (ctypes.c_void_p * 16) * 3), ("dst", ctypes.c_void_p * 3), ("channels", ctypes.c_int32 * 3),
                 ("hw", ctypes.c_int32 * 3), ("levels", ctypes.c_int32), ("n_views", ctypes.c_int32)]
+
+
+class GtCropDesc(ctypes.Structure):
+    """include/eprecon_hip.h: eprecon_gt_crop_desc"""
+    _fields_ = ([(n, ctypes.c_void_p * 3) for n in ("tsdf_full", "rgb_full", "semantic_full", "instance_full")]
+                + [("full_dims", (ctypes.c_int32 * 3) * 3), ("levels", ctypes.c_int32), ("dims", ctypes.c_int32 * 3),
+                   ("voxel_size", ctypes.c_float), ("origin_partial", ctypes.c_float * 3), ("old_origin", ctypes.c_float * 3),
+                   ("transform", ctypes.c_float * 12)]
+                + [(n, ctypes.c_void_p * 3) for n in ("tsdf_out", "rgb_out", "semantic_out", "instance_out")])
 
 
 class ConvDesc(ctypes.Structure):

@@ -713,6 +713,44 @@ int eprecon_tsdf_integrate_async(float *tsdf, float *weight, const int32_t *dims
                                  int variant, uint8_t *occ_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Fragment ground truth cut out of a scene's full volumes  (the data-preparation side)
+ *
+ * Replaces  the grid_sample part of RandomTransformSpace.transform     datasets/transforms.py:263-359,367-424
+ * One launch per sample fills the targets of all `levels` (<= 3) resolutions.  Level l has
+ * ceil(dims / 2^l) output voxels per axis (the reference's `::2**l` slices of the finest coordinates) and
+ * samples the scene volume of that level, full_dims[l] cells (x-major; the levels' dims are independent).
+ * Per output voxel i (finest cells i * 2^l), in fp32 and the reference's operation order:
+ *   X = i * voxel_size + origin_partial;  w = transform[:3,:] @ [X,1];  c = (w - old_origin) / voxel_size / 2^l;
+ *   n = 2 c / (D - 1) - 1;  u = ((n + 1) D - 1) / 2   (grid_sample, align_corners = False);  nearest = rint(u)
+ *   tsdf_out      the nearest value; the trilinear value (outside corners count 0) where |nearest| < 1;
+ *                 1 where some |n| >= 1
+ *   rgb_out [.,3] / semantic_out / instance_out   the nearest value as f32, 0 out of range or where some |n| >= 1
+ * transform f32[3][4]: rows 0..2 of the inverse augmentation (HOST values, like origin_partial / old_origin:
+ * the struct is read during the call).  rgb_full f32[X,Y,Z,3]; semantic_full / instance_full int32.  The colour,
+ * semantic and instance pointers of a level may be NULL (source and output together): the TSDF-only form.
+ * EPRECON_ERR_ARG: NULL tsdf pointers, a source without its output, levels outside 1..3, dims <= 0;
+ * EPRECON_ERR_UNSUPPORTED: a scene axis of one cell, more than 2^31 - 1 cells.  No workspace, no host read.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct eprecon_gt_crop_desc {
+    const float *tsdf_full[3];
+    const float *rgb_full[3];
+    const int32_t *semantic_full[3];
+    const int32_t *instance_full[3];
+    int32_t full_dims[3][3];
+    int32_t levels;
+    int32_t dims[3];          /* the fragment volume at the finest level */
+    float voxel_size;         /* of the finest level */
+    float origin_partial[3];
+    float old_origin[3];      /* world position of cell (0,0,0) of the scene volumes */
+    float transform[12];
+    float *tsdf_out[3];
+    float *rgb_out[3];
+    float *semantic_out[3];
+    float *instance_out[3];
+} eprecon_gt_crop_desc;
+int eprecon_gt_crop_async(const eprecon_gt_crop_desc *desc, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Scene mesh extraction: marching cubes on the dense scene TSDF  (scene output path)
  *
  * Replaces  skimage.measure.marching_cubes(tsdf_vol, level=0) + the vertex label lookups of
