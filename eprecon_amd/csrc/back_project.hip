@@ -778,12 +778,14 @@ __device__ __forceinline__ unsigned long long to_fixed(float v)
     const double x = fmin(fmax((double)v * kFixScale, -9.0e18), 9.0e18);
     return (unsigned long long)__double2ll_rn(x);           // two's complement: an unsigned add is a signed add
 }
-// A non-finite contribution (a diverging training run) must stay visible: the clamp above would turn NaN / Inf into a finite
-// +-8.2e6.  Such a contribution is not added; the element of the fp32 output (zeroed by the caller) is marked NaN instead — a
-// plain store of one value, so still independent of the order — and the conversion below leaves marked elements alone.
+// A contribution the fixed-point word cannot hold must stay visible: the clamp above would turn NaN / Inf, and any finite value
+// beyond +-8.2e6, into a finite +-8.2e6.  Such a contribution (non-finite, or |v| > kFixMax) is not added; the element of the
+// fp32 output (zeroed by the caller) is marked NaN instead — a plain store of one value, so still independent of the order — and
+// the conversion below leaves marked elements alone.  (A SUM of in-range contributions beyond 2^23 still wraps: see the header.)
+constexpr float kFixMax = 8.0e6f;   // < 9.0e18 / 2^40 = 8.19e6
 __device__ __forceinline__ void fixed_add(unsigned long long *acc, float *mark, float v)
 {
-    if (__builtin_isfinite(v)) atomicAdd(acc, to_fixed(v));
+    if (fabsf(v) <= kFixMax) atomicAdd(acc, to_fixed(v));   // (false for NaN)
     else *mark = __builtin_nanf("");
 }
 __global__ void fixed_to_float_kernel(const unsigned long long *acc, long long n, float *out)
@@ -898,11 +900,25 @@ size_t gather_mlp_lds_bytes(int vox, int V, int B)
     return (size_t)vox * V * 12 + nP * sizeof(float) + (size_t)vox * 3 * 4 + (size_t)(256 / kWave) * 4 + 16;
 }
 
+// Dynamic LDS one workgroup of the gather kernels may ask for: what the device reports per workgroup (a property query), and never
+// more than 64 KiB — no kernel of this file opts in to a larger dynamic allocation (hipFuncAttributeMaxDynamicSharedMemorySize).
+size_t gather_lds_limit()
+{
+    static const size_t limit = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || v <= 0)
+            v = 64 * 1024;
+        return (size_t)(v < 64 * 1024 ? v : 64 * 1024);
+    }();
+    return limit;
+}
+
 bool gather_mlp_supported(const BpParams &p)
 {
     return p.C % 4 == 0 && p.Cs % 4 == 0 && p.V <= 32 &&
            (size_t)p.V * p.batch * p.H * p.W * p.Cs * 4 < 0x7fff0000ull &&
-           gather_mlp_lds_bytes(256, p.V, p.batch) <= 64 * 1024;
+           gather_mlp_lds_bytes(256, p.V, p.batch) <= gather_lds_limit();
 }
 
 template <int VOX, int MODE, int U>
@@ -1085,7 +1101,11 @@ int eprecon_back_project_async(const int32_t *coords, int64_t n, const float *or
     // Tile = voxels handed to one 256-thread workgroup of the gather kernel.  Short lists get
     // small tiles so that the launch still covers the 256 CUs with several waves each
     // (13,824 voxels -> 864 workgroups of 16; 110,592 -> 1,728 of 64).
-    const int vox = n >= 512 * 1024 ? 256 : (n >= 48 * 1024 ? 64 : 16);
+    int vox = n >= 512 * 1024 ? 256 : (n >= 48 * 1024 ? 64 : 16);
+    // bp_gather_kernel<256> stages 8 bytes per (voxel, view): more than a workgroup may have from 29 views on (65,936 bytes at
+    // V = 29, B = 1).  Such a list takes the 64-voxel tile instead (17,648 bytes at V = 32); decided before any launch, because the
+    // count kernel's tile totals must match the gather's tile.
+    if (vox == 256 && !gather_mlp_supported(p) && gather_lds_bytes(256, n_views, batch) > gather_lds_limit()) vox = 64;
     const int ntile = (int)ep::ceil_div(n, vox);
     const int nblk_count = (int)ep::ceil_div(n, 256);
     const size_t lds_count = ((size_t)n_views * batch * 12 + batch + 256 / ep::kWave) * 4 + 16;

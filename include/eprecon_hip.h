@@ -1112,7 +1112,10 @@ int eprecon_back_project_backward_async(const int32_t *coords_valid, int64_t n_v
                                         int channels, int height, int width, int mode, const float *dout, int ld_dout,
                                         const float *dmean, float *dfeats_nhwc, void *stream);
 /* the same, run-to-run bit-identical: contributions are accumulated as 64-bit fixed point (2^-40 resolution, |sum| < 8.4e6) with
- * integer atomics — order-independent — in `workspace` (eprecon_back_project_backward_workspace_bytes) and converted at the end */
+ * integer atomics — order-independent — in `workspace` (eprecon_back_project_backward_workspace_bytes) and converted at the end.
+ * A single contribution (tap weight x gradient) that the word cannot hold — NaN, Inf, or finite with magnitude above 8.0e6 — is not
+ * added: the map element it touches comes back NaN, exactly as for a non-finite gradient.  The SUM of in-range contributions to one
+ * element is the caller's to keep below 2^23 = 8.4e6 (it wraps beyond). */
 size_t eprecon_back_project_backward_workspace_bytes(int batch, int n_views, int channels, int height, int width);
 int eprecon_back_project_backward_det_async(const int32_t *coords_valid, int64_t n_valid, const float *origin, int batch,
                                             float voxel_size, const float *feats_nhwc, const float *krcam, int n_views,
