@@ -4,14 +4,17 @@
 // ops/back_project.py:5-80 and the sample + mean/variance block of
 // Occupancy_Initialization.forward (models/occupancy_initialization.py:79-128).
 //
-// Pipeline per call (all on the caller's stream):
-//   [nchw_to_nhwc]   re-layout of the V*B feature maps to channels-last, so that the C channels of
-//                    one bilinear tap are one contiguous 4*C-byte run (skipped when the caller
-//                    already holds channels-last maps);
-//   bp_count         one thread per voxel: 9 projections, visible-view count (float, all N),
-//                    per-block valid totals by wave ballot + popcount, per-batch valid counts;
-//   bp_scan          exclusive scan of the block totals (one workgroup) -> output offsets, n_valid;
-//   bp_gather        phase 1, one thread per voxel: re-project, stable in-block compaction by
+// Pipeline per call (all on the caller's stream): prepare -> gather on NCHW maps, count -> gather on channels-last maps
+//   bp_prepare       one grid, two independent halves behind a block-uniform branch:
+//                    re-layout of the V*B feature maps to channels-last, so that the C channels of one bilinear tap are
+//                    one contiguous 4*C-byte run (no such blocks when the caller already holds channels-last maps:
+//                    then the launch is bp_count alone);
+//                    count, one thread per voxel: 9 projections, visible-view count (float, all N), per-tile valid
+//                    totals by wave ballot + popcount, per-batch valid counts;
+//   bp_gather        prologue: the output row of the tile = sum of the tile totals in front of it (tile_base; the
+//                    workgroup of the last tile publishes n_valid).  Lists of more than EPRECON_BP_FOLD tiles get a
+//                    bp_scan launch in front instead (exclusive scan of the totals, one workgroup);
+//                    phase 1, one thread per voxel: re-project, stable in-block compaction by
 //                    ballot/prefix-sum, pixel coordinates of every (voxel, view) staged in LDS;
 //                    phase 2, one thread per (valid voxel, 4-channel group): bilinear gather of
 //                    the visible views with 16-byte loads, mean (or two-sweep variance) in
@@ -64,7 +67,11 @@ struct BpParams {
     float *out_grid;
     uint8_t *out_mask;
     int32_t *n_valid_dev;  // [1 + B]
-    int32_t *block_offsets;
+    int32_t *block_offsets;  // exclusive scan of the tile totals (bp_scan_kernel), or the raw totals when `fold` is set
+    int fold;                // 1: no scan launch ran; every gather workgroup sums the totals in front of its tile (tile_base)
+    int ntile;               // tiles of the gather (= its grid)
+    const int32_t *blk_batch;  // [nblk_count][batch] per-batch valid counts of the count workgroups (batch > 1), else null
+    int nblk_count;
     int xcd_slabs;  // 1 (default): every XCD walks one contiguous range of tiles (ep::xcd_remap); 0: tile = hardware block id
 };
 
@@ -152,10 +159,9 @@ __device__ __forceinline__ void stage_matrices(float *sP, const float *krcam, in
 // One thread per voxel, 256 per workgroup.  The valid totals are produced per TILE of VOX consecutive
 // voxels (VOX = 256, 64 or 16: the tile the gather kernel hands to one workgroup).
 template <int VOX>
-__global__ __launch_bounds__(256) void bp_count_kernel(BpParams p, int32_t *tile_sums, int32_t *blk_batch)
+__device__ __forceinline__ void count_body(char *smem, const BpParams &p, int32_t *tile_sums, int32_t *blk_batch, int bid)
 {
     constexpr int BLOCK = 256;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     float *sP = reinterpret_cast<float *>(smem);
     int *sBatch = reinterpret_cast<int *>(sP + p.V * p.batch * 12);
     int *sWave = sBatch + p.batch;
@@ -164,7 +170,7 @@ __global__ __launch_bounds__(256) void bp_count_kernel(BpParams p, int32_t *tile
     for (int b = tid; b < p.batch; b += BLOCK) sBatch[b] = 0;
     __syncthreads();
 
-    const int i = blockIdx.x * BLOCK + tid;
+    const int i = bid * BLOCK + tid;
     bool valid = false;
     int vbatch = 0;
     if (i < p.n) {
@@ -203,7 +209,7 @@ __global__ __launch_bounds__(256) void bp_count_kernel(BpParams p, int32_t *tile
         if (tid < BLOCK / VOX) {
             int t = 0;
             for (int w = 0; w < WPT; ++w) t += sWave[tid * WPT + w];
-            const int tile = blockIdx.x * (BLOCK / VOX) + tid;
+            const int tile = bid * (BLOCK / VOX) + tid;
             if ((long long)tile * VOX < p.n) tile_sums[tile] = t;
         }
     } else {
@@ -214,8 +220,15 @@ __global__ __launch_bounds__(256) void bp_count_kernel(BpParams p, int32_t *tile
     // cost ~40 us on the dense 96^3 level: device-scope atomics serialise at the memory side)
     if (blk_batch) {
         __syncthreads();
-        for (int b = tid; b < p.batch; b += BLOCK) blk_batch[(size_t)blockIdx.x * p.batch + b] = sBatch[b];
+        for (int b = tid; b < p.batch; b += BLOCK) blk_batch[(size_t)bid * p.batch + b] = sBatch[b];
     }
+}
+
+template <int VOX>
+__global__ __launch_bounds__(256) void bp_count_kernel(BpParams p, int32_t *tile_sums, int32_t *blk_batch)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    count_body<VOX>(smem, p, tile_sums, blk_batch, (int)blockIdx.x);
 }
 
 // exclusive scan of the block totals, one workgroup; also publishes n_valid
@@ -268,6 +281,86 @@ __global__ __launch_bounds__(1024) void bp_scan_kernel(int32_t *block_sums, int 
             }
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The scan folded into the gather (BpParams::fold): the count launch has finished, so its tile totals are plain
+// read-only data, and a gather workgroup gets the output row of its tile by summing the totals in front of it
+// (the pattern of kernel_map.hip's scan_apply<true>) -- at 3,456 tiles at most 13.5 four-byte L2 loads per
+// thread -- instead of the whole chip waiting for one scanning workgroup between two launches.  No look-back,
+// no ticket, no spin: nothing here waits for another workgroup.
+//   tile_base_partials   before phase 1: per-wave partial sums -> sFold (2 x BLOCK/64 ints)
+//   tile_base_finish     after the next barrier of the caller (block_exclusive_rank's): the sums; the workgroup
+//                        of the last tile publishes n_valid_dev[0 .. B] (what bp_scan_kernel published), and
+//                        has to do so before the caller's `if (nloc == 0) return;`
+// `all` (block-uniform): the sum runs over every tile, which also gives n_valid -- wanted by that last workgroup
+// and by every workgroup when out_grid / out_mask are written (n_valid is their view stride).
+// ---------------------------------------------------------------------------------------------
+struct TileBase {
+    int base, n_valid;
+};
+
+__device__ __forceinline__ bool tile_base_all(const BpParams &p, int lb)
+{
+    return p.out_grid != nullptr || p.out_mask != nullptr || lb == p.ntile - 1;
+}
+
+__device__ __forceinline__ void tile_base_partials(const BpParams &p, int lb, int *sFold)
+{
+    constexpr int BLOCK = 256;
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid / kWave;
+    const int end = tile_base_all(p, lb) ? p.ntile : lb;
+    int acc = 0, tot = 0;
+#pragma unroll 4
+    for (int t = tid; t < end; t += BLOCK) {
+        const int x = p.block_offsets[t];
+        tot += x;
+        acc += t < lb ? x : 0;
+    }
+#pragma unroll
+    for (int d = kWave / 2; d > 0; d >>= 1) {
+        acc += __shfl_xor(acc, d);
+        tot += __shfl_xor(tot, d);
+    }
+    if (lane == 0) {
+        sFold[wid] = acc;
+        sFold[BLOCK / kWave + wid] = tot;
+    }
+}
+
+__device__ __forceinline__ TileBase tile_base_finish(const BpParams &p, int lb, int *sFold)
+{
+    constexpr int BLOCK = 256, NW = BLOCK / kWave;
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid / kWave;
+    TileBase r = {0, 0};
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        r.base += sFold[w];
+        r.n_valid += sFold[NW + w];
+    }
+    if (lb == p.ntile - 1) {   // block-uniform
+        if (tid == 0) {
+            p.n_valid_dev[0] = r.n_valid;
+            if (p.batch == 1) p.n_valid_dev[1] = r.n_valid;
+        }
+        if (p.batch > 1 && p.blk_batch) {
+            for (int b = 0; b < p.batch; ++b) {
+                int x = 0;
+                for (int i = tid; i < p.nblk_count; i += BLOCK) x += p.blk_batch[(size_t)i * p.batch + b];
+#pragma unroll
+                for (int d = kWave / 2; d > 0; d >>= 1) x += __shfl_xor(x, d);
+                __syncthreads();   // (sFold: the sums above, then the row before, have been read)
+                if (lane == 0) sFold[wid] = x;
+                __syncthreads();
+                if (tid == 0) {
+                    int t = 0;
+                    for (int w = 0; w < NW; ++w) t += sFold[w];
+                    p.n_valid_dev[1 + b] = t;
+                }
+            }
+        }
+    }
+    return r;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -373,10 +466,12 @@ __global__ __launch_bounds__(256) void bp_gather_kernel(BpParams p)
     int *sSlot = sBatch + VOX;                                           // [VOX] rank -> thread
     int *sOut = sSlot + VOX;                                             // [VOX] thread -> output row
     int *sWave = sOut + VOX;                                             // [BLOCK/64]
+    int *sFold = sWave + BLOCK / kWave;                                  // [2 * BLOCK/64] (tile_base)
 
     const int tid = threadIdx.x;
     const int lb = p.xcd_slabs ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
     stage_matrices(sP, p.krcam, p.V * p.batch, tid, BLOCK);
+    if (p.fold) tile_base_partials(p, lb, sFold);
     __syncthreads();
 
     const int e = lb * VOX + tid;
@@ -408,9 +503,11 @@ __global__ __launch_bounds__(256) void bp_gather_kernel(BpParams p)
     }
     int nloc;
     const int rank = block_exclusive_rank<BLOCK>(valid, sWave, nloc);
+    TileBase tb = {0, 0};
+    if (p.fold) tb = tile_base_finish(p, lb, sFold);
     if (nloc == 0) return;
-    const int base = p.block_offsets[lb];
-    const int n_valid = p.n_valid_dev[0];
+    const int base = p.fold ? tb.base : p.block_offsets[lb];
+    const int n_valid = p.fold ? tb.n_valid : p.n_valid_dev[0];
     const int cout = (MODE == EPRECON_BP_MEAN_DEPTH) ? p.C + 1 : p.C;
     if (valid) {
         const int o = base + rank;
@@ -491,6 +588,11 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 //             first) are issued before the first fma; slots past the last visible view point out of
 //             the buffer range, which costs no memory traffic.  Views accumulate in ascending order.
 // ---------------------------------------------------------------------------------------------
+// Tiles up to which the scan is folded into the gather (tile_base).  >= 3,456 (dense 96^3 at 256 voxels); the sweep of list
+// lengths behind the figure is profiles/r12/fold_cap.txt.  tests/test_back_project_launches_gpu.py restates the
+// figure (DEFAULT_CAP) and reads the tile totals at offset 0 of the workspace: change them together.
+constexpr int kFoldCapDefault = 6144;
+
 constexpr int kOobOffset = (int)0x80000000u;  // >= num_records (maps are limited to < 2 GiB here)
 
 template <int U, class F>
@@ -547,11 +649,13 @@ __global__ __launch_bounds__(256) void bp_gather_mlp_kernel(BpParams p)
     int *sSlot = reinterpret_cast<int *>(sVis + VOX);                     // [VOX] rank -> voxel
     int *sOut = sSlot + VOX;                                              // [VOX] voxel -> output row
     int *sWave = sOut + VOX;                                              // [BLOCK/64]
+    int *sFold = sWave + BLOCK / kWave;                                   // [2 * BLOCK/64] (tile_base)
 
     const int tid = threadIdx.x;
     const int lb = p.xcd_slabs ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
     stage_matrices(sP, p.krcam, p.V * p.batch, tid, BLOCK);
     if (VPT > 1 && tid < VOX) sVis[tid] = 0;
+    if (p.fold) tile_base_partials(p, lb, sFold);
     __syncthreads();
 
     const float wm1 = (float)(p.W - 1), hm1 = (float)(p.H - 1);
@@ -586,11 +690,13 @@ __global__ __launch_bounds__(256) void bp_gather_mlp_kernel(BpParams p)
     const bool valid = tid < VOX && in_batch && cnt >= p.min_view;
     int nloc;
     const int rank = block_exclusive_rank<BLOCK>(valid, sWave, nloc);
+    TileBase tb = {0, 0};
+    if (p.fold) tb = tile_base_finish(p, lb, sFold);
     if (nloc == 0) return;
-    const int n_valid = p.n_valid_dev[0];
+    const int n_valid = p.fold ? tb.n_valid : p.n_valid_dev[0];
     const int cout = (MODE == EPRECON_BP_MEAN_DEPTH) ? p.C + 1 : p.C;
     if (valid) {
-        const int o = p.block_offsets[lb] + rank;
+        const int o = (p.fold ? tb.base : p.block_offsets[lb]) + rank;
         sSlot[rank] = tid;
         sOut[tid] = o;
         if (VPT == 1) sVis[tid] = vis;
@@ -697,28 +803,83 @@ __global__ __launch_bounds__(1024) void bp_depth_norm_kernel(float *out_feats, i
 // NCHW -> NHWC through an LDS tile: reads coalesced along H*W, writes coalesced along (pixel, C)
 // ---------------------------------------------------------------------------------------------
 constexpr int kTrPix = 64;
+// One 64-pixel tile of one map.  VEC4 (hw % 4 == 0, Cs % 4 == 0, 16-byte aligned bases): 16 bytes per lane on both sides -- four
+// pixels of one channel in, four channels of one pixel out; otherwise 4 bytes per lane.  A copy either way: the same bits.
+template <bool VEC4>
+__device__ __forceinline__ void relayout_body(char *smem, const float *__restrict__ in, float *__restrict__ out, int C, int hw,
+                                              int Cs, int map, int p0)
+{
+    float *tile = reinterpret_cast<float *>(smem);  // [C][kTrPix + 1]
+    const int npix = min(kTrPix, hw - p0);
+    const float *src = in + (size_t)map * C * hw;
+    float *dst = out + (size_t)map * hw * Cs + (size_t)p0 * Cs;
+    if constexpr (VEC4) {
+        constexpr int G = kTrPix / 4;
+        for (int e = threadIdx.x; e < C * G; e += 256) {
+            const int c = e / G, px = (e - c * G) * 4;
+            if (px < npix) {   // (npix is a multiple of 4 here: px + 3 < npix)
+                const float4 v = *reinterpret_cast<const float4 *>(src + (size_t)c * hw + p0 + px);
+                float *t = tile + c * (kTrPix + 1) + px;
+                t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
+            }
+        }
+        __syncthreads();
+        const int Q = Cs / 4;
+        for (int e = threadIdx.x; e < npix * Q; e += 256) {  // pad channels (Cs > C) are written as zeros
+            const int px = e / Q, c = (e - px * Q) * 4;
+            const float *t = tile + c * (kTrPix + 1) + px;
+            float4 v;
+            v.x = c + 0 < C ? t[0 * (kTrPix + 1)] : 0.0f;
+            v.y = c + 1 < C ? t[1 * (kTrPix + 1)] : 0.0f;
+            v.z = c + 2 < C ? t[2 * (kTrPix + 1)] : 0.0f;
+            v.w = c + 3 < C ? t[3 * (kTrPix + 1)] : 0.0f;
+            reinterpret_cast<float4 *>(dst)[e] = v;
+        }
+    } else {
+        for (int e = threadIdx.x; e < C * kTrPix; e += 256) {
+            const int c = e / kTrPix, px = e - c * kTrPix;
+            if (px < npix) tile[c * (kTrPix + 1) + px] = src[(size_t)c * hw + p0 + px];
+        }
+        __syncthreads();
+        for (int e = threadIdx.x; e < npix * Cs; e += 256) {  // pad channels (Cs > C) are written as zeros
+            const int px = e / Cs, c = e - px * Cs;
+            dst[e] = c < C ? tile[c * (kTrPix + 1) + px] : 0.0f;
+        }
+    }
+}
+
+bool relayout_vec4(const void *in, const void *out, int hw, int Cs)
+{
+    return hw % 4 == 0 && Cs % 4 == 0 && (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
+}
+
 // zero / zero_n (optional): int32 words the first block clears on its way — the valid-voxel counters of the back-projection
-// this re-layout is the first launch of (one launch less than a memset in front of it)
+// this re-layout is the first launch of (the EPRECON_BP_FOLD=0 chain: one launch less than a memset in front of it)
+template <bool VEC4>
 __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float *__restrict__ in,
                                                            float *__restrict__ out, int C, int hw, int Cs,
                                                            int32_t *zero = nullptr, int zero_n = 0)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float *tile = reinterpret_cast<float *>(smem);  // [C][kTrPix + 1]
     if (blockIdx.x == 0 && blockIdx.y == 0 && (int)threadIdx.x < zero_n) zero[threadIdx.x] = 0;
-    const int map = blockIdx.y;
-    const int p0 = blockIdx.x * kTrPix;
-    const int npix = min(kTrPix, hw - p0);
-    const float *src = in + (size_t)map * C * hw;
-    float *dst = out + (size_t)map * hw * Cs + (size_t)p0 * Cs;
-    for (int e = threadIdx.x; e < C * kTrPix; e += 256) {
-        const int c = e / kTrPix, px = e - c * kTrPix;
-        if (px < npix) tile[c * (kTrPix + 1) + px] = src[(size_t)c * hw + p0 + px];
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < npix * Cs; e += 256) {  // pad channels (Cs > C) are written as zeros
-        const int px = e / Cs, c = e - px * Cs;
-        dst[e] = c < C ? tile[c * (kTrPix + 1) + px] : 0.0f;
+    relayout_body<VEC4>(smem, in, out, C, hw, Cs, (int)blockIdx.y, (int)blockIdx.x * kTrPix);
+}
+
+// The first launch of a back-projection on NCHW maps: blocks [0, R) re-lay the maps out (R = maps x 64-pixel tiles), the rest
+// count (count_body).  The two halves do not depend on each other; the gather that follows needs both.  The count is
+// arithmetic on 16 bytes per voxel and runs under the copy.  Dynamic LDS: the larger of the two bodies'.
+template <int VOX, bool VEC4>
+__global__ __launch_bounds__(256) void bp_prepare_kernel(BpParams p, int32_t *tile_sums, int32_t *blk_batch,
+                                                         const float *__restrict__ in, float *__restrict__ out, int hw,
+                                                         int tiles, int R)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int bid = blockIdx.x;
+    if (bid < R) {   // block-uniform
+        const int map = bid / tiles;
+        relayout_body<VEC4>(smem, in, out, p.C, hw, p.Cs, map, (bid - map * tiles) * kTrPix);
+    } else {
+        count_body<VOX>(smem, p, tile_sums, blk_batch, bid - R);
     }
 }
 
@@ -869,7 +1030,7 @@ size_t gather_lds_bytes(int vox, int V, int B)
 {
     const size_t nP = ((size_t)V * B * 12 + 3) & ~(size_t)3;
     return (size_t)vox * V * sizeof(float2) + nP * sizeof(float) + (size_t)vox * 5 * 4 +
-           (size_t)(256 / kWave) * 4 + 16;
+           (size_t)(256 / kWave) * 4 * 3;   // (sWave, sFold)
 }
 
 template <int VOX, int MODE>
@@ -897,7 +1058,7 @@ int launch_gather(const BpParams &p, int nblk, hipStream_t st)
 size_t gather_mlp_lds_bytes(int vox, int V, int B)
 {
     const size_t nP = ((size_t)V * B * 12 + 3) & ~(size_t)3;
-    return (size_t)vox * V * 12 + nP * sizeof(float) + (size_t)vox * 3 * 4 + (size_t)(256 / kWave) * 4 + 16;
+    return (size_t)vox * V * 12 + nP * sizeof(float) + (size_t)vox * 3 * 4 + (size_t)(256 / kWave) * 4 * 3;   // (sWave, sFold)
 }
 
 // Dynamic LDS one workgroup of the gather kernels may ask for: what the device reports per workgroup (a property query), and never
@@ -1010,8 +1171,12 @@ int eprecon_nchw_to_nhwc_async(const float *in, float *out, int maps, int channe
     const size_t lds = (size_t)channels * (kTrPix + 1) * sizeof(float);
     if (lds > 64 * 1024) return EPRECON_ERR_UNSUPPORTED;
     const dim3 grid((unsigned)ep::ceil_div(hw, kTrPix), (unsigned)maps);
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel, grid, dim3(256), lds, (hipStream_t)stream, in, out,
-                       channels, hw, channels);
+    if (relayout_vec4(in, out, hw, channels))
+        hipLaunchKernelGGL(nchw_to_nhwc_kernel<true>, grid, dim3(256), lds, (hipStream_t)stream, in, out, channels, hw, channels,
+                           (int32_t *)nullptr, 0);
+    else
+        hipLaunchKernelGGL(nchw_to_nhwc_kernel<false>, grid, dim3(256), lds, (hipStream_t)stream, in, out, channels, hw, channels,
+                           (int32_t *)nullptr, 0);
     EP_LAUNCH_CHECK();
     return EPRECON_OK;
 }
@@ -1061,9 +1226,23 @@ int eprecon_back_project_async(const int32_t *coords, int64_t n, const float *or
         return EPRECON_ERR_WORKSPACE;
     if ((size_t)n_views * batch * channels * height * width > 0x7fffffffull) return EPRECON_ERR_UNSUPPORTED;
 
-    // (the counters are cleared by the re-layout launch below when there is one: NCHW features, <= 255 batch elements)
-    const bool clear_in_relayout = n > 0 && feats_layout == EPRECON_LAYOUT_NCHW && batch < 256;
-    if (!clear_in_relayout) EP_HIP_CHECK(hipMemsetAsync(n_valid_dev, 0, sizeof(int32_t) * (size_t)(1 + batch), st));
+    if (feats_layout != EPRECON_LAYOUT_NCHW && feats_layout != EPRECON_LAYOUT_NHWC) return EPRECON_ERR_ARG;
+    const bool nchw = feats_layout == EPRECON_LAYOUT_NCHW;
+    // EPRECON_BP_FOLD (read per call): the largest tile count at which the gather workgroups sum the tile totals themselves
+    // (tile_base) instead of a scan launch between count and gather.  Unset: kFoldCapDefault; N > 0: N tiles; 0: the chain of
+    // four dependent launches as it was -- re-layout (clearing the counters), count, scan, gather.  Same results every way.
+    int fold_cap = kFoldCapDefault;
+    if (const char *e = getenv("EPRECON_BP_FOLD"); e && e[0]) {
+        const long v = strtol(e, nullptr, 10);
+        fold_cap = v <= 0 ? 0 : (v > 0x7fffffffL ? 0x7fffffff : (int)v);
+    }
+    const bool chain4 = fold_cap == 0;
+    // The counters: every word of n_valid_dev[0 .. B] is written by the scan launch or by the gather's last workgroup, so only
+    // the empty list needs them cleared.  (The four-launch chain clears them as it always did: inside the re-layout launch when
+    // there is one -- NCHW features, <= 255 batch elements -- else by a memset.)
+    const bool clear_in_relayout = chain4 && n > 0 && nchw && batch < 256;
+    if (n == 0 || (chain4 && !clear_in_relayout))
+        EP_HIP_CHECK(hipMemsetAsync(n_valid_dev, 0, sizeof(int32_t) * (size_t)(1 + batch), st));
     if (n == 0) return EPRECON_OK;
 
     char *ws = reinterpret_cast<char *>(workspace);
@@ -1071,24 +1250,14 @@ int eprecon_back_project_async(const int32_t *coords, int64_t n, const float *or
     ws += ep::align_up((size_t)ep::ceil_div(n, 16) * sizeof(int32_t), 256);
     int32_t *blk_batch = reinterpret_cast<int32_t *>(ws);
     ws += ep::align_up((size_t)ep::ceil_div(n, 256) * batch * sizeof(int32_t), 256);
-    const float *nhwc = feats;
-    int pix_stride = channels;
-    if (feats_layout == EPRECON_LAYOUT_NCHW) {
-        float *tmp = reinterpret_cast<float *>(ws);
-        const size_t lds_t = (size_t)channels * (kTrPix + 1) * sizeof(float);
-        if (lds_t > 64 * 1024) return EPRECON_ERR_UNSUPPORTED;
-        hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3((unsigned)ep::ceil_div(height * width, kTrPix), (unsigned)(n_views * batch)),
-                           dim3(256), lds_t, st, feats, tmp, channels, height * width, pix_stride, n_valid_dev, 1 + batch);
-        EP_LAUNCH_CHECK();
-        nhwc = tmp;
-        ws += ep::align_up((size_t)n_views * batch * pix_stride * height * width * sizeof(float), 256);
-    } else if (feats_layout != EPRECON_LAYOUT_NHWC) {
-        return EPRECON_ERR_ARG;
-    }
+    const int pix_stride = channels;
+    float *tmp = reinterpret_cast<float *>(ws);   // the channels-last maps of an NCHW call
+    const size_t lds_t = (size_t)channels * (kTrPix + 1) * sizeof(float);
+    if (nchw && lds_t > 64 * 1024) return EPRECON_ERR_UNSUPPORTED;
 
     BpParams p;
     p.coords = coords; p.n = (int)n; p.origin = origin; p.batch = batch; p.voxel_size = voxel_size;
-    p.feats_nhwc = nhwc; p.krcam = krcam; p.V = n_views; p.C = channels; p.Cs = pix_stride; p.H = height; p.W = width;
+    p.feats_nhwc = nchw ? tmp : feats; p.krcam = krcam; p.V = n_views; p.C = channels; p.Cs = pix_stride; p.H = height; p.W = width;
     p.min_view = min_view; p.out_feats = out_feats; p.out_mean = out_mean; p.out_coords = out_coords;
     p.count = count; p.out_grid = out_grid; p.out_mask = out_mask; p.n_valid_dev = n_valid_dev;
     p.block_offsets = block_sums;
@@ -1102,24 +1271,51 @@ int eprecon_back_project_async(const int32_t *coords, int64_t n, const float *or
     // small tiles so that the launch still covers the 256 CUs with several waves each
     // (13,824 voxels -> 864 workgroups of 16; 110,592 -> 1,728 of 64).
     int vox = n >= 512 * 1024 ? 256 : (n >= 48 * 1024 ? 64 : 16);
-    // bp_gather_kernel<256> stages 8 bytes per (voxel, view): more than a workgroup may have from 29 views on (65,936 bytes at
-    // V = 29, B = 1).  Such a list takes the 64-voxel tile instead (17,648 bytes at V = 32); decided before any launch, because the
+    // bp_gather_kernel<256> stages 8 bytes per (voxel, view): more than a workgroup may have from 29 views on (65,952 bytes at
+    // V = 29, B = 1).  Such a list takes the 64-voxel tile instead (17,664 bytes at V = 32); decided before any launch, because the
     // count kernel's tile totals must match the gather's tile.
     if (vox == 256 && !gather_mlp_supported(p) && gather_lds_bytes(256, n_views, batch) > gather_lds_limit()) vox = 64;
     const int ntile = (int)ep::ceil_div(n, vox);
     const int nblk_count = (int)ep::ceil_div(n, 256);
     const size_t lds_count = ((size_t)n_views * batch * 12 + batch + 256 / ep::kWave) * 4 + 16;
     int32_t *bb = batch > 1 ? blk_batch : nullptr;
-    if (vox == 256)
-        hipLaunchKernelGGL((bp_count_kernel<256>), dim3(nblk_count), dim3(256), lds_count, st, p, block_sums, bb);
-    else if (vox == 64)
-        hipLaunchKernelGGL((bp_count_kernel<64>), dim3(nblk_count), dim3(256), lds_count, st, p, block_sums, bb);
-    else
-        hipLaunchKernelGGL((bp_count_kernel<16>), dim3(nblk_count), dim3(256), lds_count, st, p, block_sums, bb);
-    EP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bp_scan_kernel, dim3(1), dim3(1024), 0, st, block_sums, ntile, n_valid_dev,
-                       (const int32_t *)bb, nblk_count, batch);
-    EP_LAUNCH_CHECK();
+    p.fold = (!chain4 && ntile <= fold_cap) ? 1 : 0;
+    p.ntile = ntile; p.blk_batch = bb; p.nblk_count = nblk_count;
+
+    if (nchw && !chain4) {
+        // prepare: re-layout and count in one grid (bp_prepare_kernel)
+        const int hw = height * width, tiles = ep::ceil_div(hw, kTrPix), R = tiles * n_views * batch;
+        const size_t lds_p = lds_t > lds_count ? lds_t : lds_count;
+        const dim3 grid((unsigned)(R + nblk_count));
+        const bool v4 = relayout_vec4(feats, tmp, hw, pix_stride);
+#define EP_PREPARE(VOX)                                                                                                          \
+    if (v4) hipLaunchKernelGGL((bp_prepare_kernel<VOX, true>), grid, dim3(256), lds_p, st, p, block_sums, bb, feats, tmp, hw, tiles, R); \
+    else hipLaunchKernelGGL((bp_prepare_kernel<VOX, false>), grid, dim3(256), lds_p, st, p, block_sums, bb, feats, tmp, hw, tiles, R)
+        if (vox == 256) { EP_PREPARE(256); }
+        else if (vox == 64) { EP_PREPARE(64); }
+        else { EP_PREPARE(16); }
+#undef EP_PREPARE
+        EP_LAUNCH_CHECK();
+    } else {
+        if (nchw) {   // (only the four-launch chain comes here with NCHW maps; it clears the counters on the way for batch < 256)
+            hipLaunchKernelGGL(nchw_to_nhwc_kernel<false>, dim3((unsigned)ep::ceil_div(height * width, kTrPix), (unsigned)(n_views * batch)),
+                               dim3(256), lds_t, st, feats, tmp, channels, height * width, pix_stride,
+                               clear_in_relayout ? n_valid_dev : (int32_t *)nullptr, clear_in_relayout ? 1 + batch : 0);
+            EP_LAUNCH_CHECK();
+        }
+        if (vox == 256)
+            hipLaunchKernelGGL((bp_count_kernel<256>), dim3(nblk_count), dim3(256), lds_count, st, p, block_sums, bb);
+        else if (vox == 64)
+            hipLaunchKernelGGL((bp_count_kernel<64>), dim3(nblk_count), dim3(256), lds_count, st, p, block_sums, bb);
+        else
+            hipLaunchKernelGGL((bp_count_kernel<16>), dim3(nblk_count), dim3(256), lds_count, st, p, block_sums, bb);
+        EP_LAUNCH_CHECK();
+    }
+    if (!p.fold) {
+        hipLaunchKernelGGL(bp_scan_kernel, dim3(1), dim3(1024), 0, st, block_sums, ntile, n_valid_dev,
+                           (const int32_t *)bb, nblk_count, batch);
+        EP_LAUNCH_CHECK();
+    }
 
     const bool prof = g_prof.on && g_prof.start;
     if (prof) EP_HIP_CHECK(hipEventRecord(g_prof.start, st));
