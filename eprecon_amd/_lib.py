@@ -120,6 +120,10 @@ SIGNATURES = {
     "eprecon_gather_rows_async": (_i, [_vp, _i, _vp, _i64, _i, _f, _vp, _i, _vp]),
     "eprecon_tsdf_integrate_async": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _vp, _vp, _f, _f, _i, _vp, _vp]),
     "eprecon_gt_crop_async": (_i, [_vp, _vp]),
+    "eprecon_label_volumes_workspace_bytes": (_sz, [_i64, _i64]),
+    "eprecon_label_volumes": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _c.c_double, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "eprecon_label_fill_workspace_bytes": (_sz, [_i, _i, _i]),
+    "eprecon_label_fill_async": (_i, [_vp, _vp, _vp, _vp, _sz, _vp]),
     "eprecon_marching_cubes_table": (_i, [_vp]),
     "eprecon_marching_cubes_workspace_bytes": (_sz, [_i, _i, _i]),
     "eprecon_marching_cubes_count": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),

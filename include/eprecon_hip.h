@@ -751,6 +751,35 @@ typedef struct eprecon_gt_crop_desc {
 int eprecon_gt_crop_async(const eprecon_gt_crop_desc *desc, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Scene ground truth from a labelled point cloud  (csrc/label_volume.hip: the offline step that writes the
+ * files the fragment ground truth above is cut from)
+ *
+ * Replaces  integrate_semantic + the coordinate step     tools/tsdf_fusion/generate_gt.py:77-114,199-202
+ *           the NearestNDInterpolator fill               datasets/scannet/label_interpolate.py:25-48
+ *
+ * eprecon_label_volumes (BLOCKING: one int32 read at the end, the label range check):
+ *   xyz / rgb f64[n,3], semantic / instance int64[n] on the device; vol_min_host f64[3], dims_host int32[3] HOST.
+ *   cell = clip(rint((xyz - vol_min) / voxel_size), 0, dim - 1) in float64, ties to even.
+ *   rgb_out f64[X,Y,Z,3]   per-cell sum in ascending point index / max(count, 1)   (bit-reproducible: no atomics)
+ *   semantic_out / instance_out int64[X,Y,Z]   the cell's most frequent label, the smallest on a tie; 0 when empty
+ *   EPRECON_ERR_ARG: a label outside [0, 32767] (the outputs are then undefined), dims <= 0, voxel_size <= 0;
+ *   EPRECON_ERR_UNSUPPORTED: more than 2^31 - 257 cells or points.
+ *
+ * eprecon_label_fill_async: vol int32[X,Y,Z] -> out int32[X,Y,Z] (out != vol), every cell the label of a nearest
+ *   non-zero cell by exact integer squared distance; all zero when vol is.  Among equidistant sites: the smallest
+ *   |dx|, then the lower x, then the smallest |dy|, the lower y, the smallest |dz|, the lower z.
+ *   EPRECON_ERR_UNSUPPORTED: an axis above 4,096 (checked before any pointer is looked at).
+ * ------------------------------------------------------------------------------------------ */
+size_t eprecon_label_volumes_workspace_bytes(int64_t n, int64_t cells);
+int eprecon_label_volumes(const double *xyz, const double *rgb, const int64_t *semantic, const int64_t *instance,
+                          int64_t n, const double *vol_min_host, double voxel_size, const int32_t *dims_host,
+                          double *rgb_out, int64_t *semantic_out, int64_t *instance_out, void *workspace,
+                          size_t workspace_bytes, void *stream);
+size_t eprecon_label_fill_workspace_bytes(int dx, int dy, int dz);
+int eprecon_label_fill_async(const int32_t *vol, const int32_t *dims_host, int32_t *out, void *workspace,
+                             size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Scene mesh extraction: marching cubes on the dense scene TSDF  (scene output path)
  *
  * Replaces  skimage.measure.marching_cubes(tsdf_vol, level=0) + the vertex label lookups of
