@@ -27,6 +27,10 @@ SIGNATURES = {
                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "eprecon_back_project": (_i, [_vp, _i64, _vp, _i, _f, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i,
                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "eprecon_back_project_phase_async": (_i, [_i, _vp, _i64, _vp, _i, _f, _vp, _i, _vp, _i, _i, _i, _i, _i, _i,
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "eprecon_back_project_rank_out": (_i, [_vp]),
+    "eprecon_init_glue": (_i, []),
     "eprecon_profile_gather_kernel": (_c.c_char_p, []),
     "eprecon_hash_capacity": (_c.c_uint32, [_i64]),
     "eprecon_hash_table_bytes": (_sz, [_c.c_uint32]),
@@ -61,6 +65,8 @@ SIGNATURES = {
     "eprecon_affine_rows_res_async": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp]),
     "eprecon_batchnorm_finalize_affine_async": (_i, [_vp, _i64, _i64, _i, _vp, _vp, _f, _vp, _vp, _vp]),
     "eprecon_affine_rows_async": (_i, [_vp, _i64, _i, _i, _vp, _vp, _i, _vp, _i, _vp]),
+    "eprecon_affine_pool2_rows_async": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp]),
+    "eprecon_affine_up2_rows_async": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp]),
     "eprecon_pixel_map_async": (_i, [_i, _i, _i, _i, _vp, _vp]),
     "eprecon_batchnorm_apply_workspace_bytes": (_sz, [_i]),
     "eprecon_batchnorm_apply_partials_async": (_i, [_vp, _i64, _i, _i, _vp, _i64, _i64, _vp, _vp, _f, _vp, _i, _i, _vp, _i,
@@ -73,6 +79,7 @@ SIGNATURES = {
     "eprecon_rowwise_layernorm_async": (_i, [_vp, _i64, _i, _i, _vp, _i, _vp, _vp, _f, _i, _i, _vp, _i, _vp]),
     "eprecon_init_select_workspace_bytes": (_sz, [_i, _i]),
     "eprecon_init_select_async": (_i, [_vp, _vp, _i64, _f, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "eprecon_init_select_dense_async": (_i, [_vp, _vp, _i64, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "eprecon_upsample_async": (_i, [_vp, _i, _vp, _i64, _i, _i, _vp, _vp, _vp]),
     "eprecon_aligned_coords_async": (_i, [_vp, _i64, _vp, _i, _f, _vp, _vp, _vp]),
     "eprecon_point_quantize_async": (_i, [_vp, _i64, _f, _vp, _vp, _vp]),

@@ -26,6 +26,26 @@ def mark_dense(coords, dims, interval, batch=1):
     return coords
 
 
+def dense_rank_buffer(coords, dims, interval):
+    """-> an int32[N + 1] device buffer for the rank volume (`rank_out` of run / run_async / view_variance) when `coords` is
+    tagged as the one-element dense raster of exactly this grid (mark_dense) and EPRECON_INIT_GLUE is on, else None: the
+    gather then writes entry -> output row (or -1) while it compacts, and sparse.DenseMap has nothing left to build"""
+    tag = getattr(coords, "_eprecon_dense", None)
+    want = (tuple(int(d) for d in dims), int(interval), 1)
+    if tag != want or not coords.is_cuda or coords.shape[0] != want[0][0] * want[0][1] * want[0][2]:
+        return None
+    if not _lib.load().eprecon_init_glue():
+        return None
+    return torch.empty(coords.shape[0] + 1, dtype=torch.int32, device=coords.device)
+
+
+def _arm_rank(lib, rank_out, n, batch):
+    """the next library call of this thread writes the rank volume (eprecon_back_project_rank_out: one-shot)"""
+    if rank_out is not None:
+        assert batch == 1 and rank_out.dtype == torch.int32 and rank_out.is_contiguous() and rank_out.numel() == n + 1
+        _lib.check(lib.eprecon_back_project_rank_out(_lib.ptr(rank_out)), "eprecon_back_project_rank_out")
+
+
 def _prep_feats(feats):
     """feats: [V, B, C, H, W] (logical shape).  Channels-last storage (stride of C == 1) is passed
     through without a copy; anything else is made NCHW-contiguous."""
@@ -66,13 +86,56 @@ class PendingBackProject:
         return res
 
 
+class CountedBackProject:
+    """the count half of a back-projection (count_async), to be handed to run_async(counted=...) with the maps"""
+
+    def __init__(self, shape, inputs, count, n_valid_dev, ws, stream):
+        self.shape, self.inputs, self.count, self.n_valid_dev, self.ws, self.stream = shape, inputs, count, n_valid_dev, ws, stream
+
+
+def count_async(coords, origin, voxel_size, feats_shape, krcam, min_view, mode=MODE_MEAN, stream=None):
+    """Queue the half of a back-projection that needs no maps — visible views per voxel, valid totals per tile — for
+    channels-last maps of logical shape feats_shape = (V, B, C, H, W) that may not exist yet.  stream: another stream to
+    queue it on behind the work queued so far (run_async waits for it); buffers are allocated on the current stream.
+    Same launches as the one-call form (eprecon_back_project_phase_async)."""
+    lib = _lib.load()
+    dev = coords.device
+    if dev.type != "cuda":
+        raise _lib.EpreconError("eprecon_amd operators need device tensors (no CPU fallback)")
+    v, b, c, h, w = (int(x) for x in feats_shape)
+    n = coords.shape[0]
+    coords_i = (coords if coords.dtype == torch.int32 else coords.to(torch.int32)).contiguous()
+    origin_f = origin.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+    krcam_f = krcam.to(device=dev, dtype=torch.float32).contiguous()
+    assert krcam_f.shape == (v, b, 4, 4) and origin_f.shape[0] == b
+    count = torch.empty((n,), dtype=torch.float32, device=dev)
+    n_valid_dev = torch.empty((1 + b,), dtype=torch.int32, device=dev)
+    # a buffer of the call's own, not the stream's grow-only scratch: it has to survive until the gather half has run
+    ws = torch.empty((lib.eprecon_back_project_workspace_bytes(n, b, v, c, h, w, LAYOUT_NHWC),), dtype=torch.uint8, device=dev)
+
+    def queue():
+        _lib.check(lib.eprecon_back_project_phase_async(
+            1, _lib.ptr(coords_i), n, _lib.ptr(origin_f), b, float(voxel_size), None, LAYOUT_NHWC, _lib.ptr(krcam_f), v, c, h, w,
+            int(min_view), mode, None, None, None, _lib.ptr(count), None, None, _lib.ptr(n_valid_dev), _lib.ptr(ws), ws.numel(),
+            _lib.current_stream()), "eprecon_back_project_phase_async")
+    if stream is None:
+        queue()
+    else:
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(stream):
+            queue()
+    return CountedBackProject((v, b, c, h, w), (coords_i, origin_f, krcam_f, float(voxel_size), int(min_view), mode), count,
+                              n_valid_dev, ws, stream)
+
+
 def run_async(coords, origin, voxel_size, feats, krcam, min_view, mode=MODE_MEAN, min_valid_per_batch=1,
-              want_grid=False, want_mean=False, hold_read=False, extra_words=0):
+              want_grid=False, want_mean=False, hold_read=False, extra_words=0, rank_out=None, counted=None):
     """Queue the back-projection on the current stream and return a PendingBackProject.
     hold_read: no host copy of the counts is queued — the caller reads `.n_valid_dev` itself, together with whatever else it
     queued on the device count `.n_valid_dev[0:1]` of the compacted rows `.coords_all` (torchsparse_utils.SpvcnnPrefetch), and
     hands the values to result_from().  extra_words: `.n_valid_dev` gets that many more int32 behind the 1 + B counts (the caller's
-    own counts, so that one tensor is read)."""
+    own counts, so that one tensor is read).  rank_out: dense_rank_buffer(...)'s buffer, or None.
+    counted: count_async(...)'s result for these very arguments — only the gather half is queued here."""
     lib = _lib.load()
     dev = feats.device
     if dev.type != "cuda":
@@ -86,32 +149,44 @@ def run_async(coords, origin, voxel_size, feats, krcam, min_view, mode=MODE_MEAN
     assert krcam_f.shape == (v, b, 4, 4) and origin_f.shape[0] == b
     feats_c, layout = _prep_feats(feats)
     cout = c + 1 if mode == MODE_MEAN_DEPTH else c
+    if counted is not None:
+        assert layout == LAYOUT_NHWC and counted.shape == (v, b, c, h, w) and not extra_words
+        assert counted.inputs[3:] == (float(voxel_size), int(min_view), mode) and counted.count.shape[0] == n
+        coords_i, origin_f, krcam_f = counted.inputs[:3]
 
     t = {"feats": torch.empty((n, cout), dtype=torch.float32, device=dev),
          "coords": torch.empty((n, 4), dtype=torch.int32, device=dev),
-         "count": torch.empty((n,), dtype=torch.float32, device=dev),
+         "count": torch.empty((n,), dtype=torch.float32, device=dev) if counted is None else counted.count,
          "mean": torch.empty((n, c), dtype=torch.float32, device=dev) if want_mean else None,
          "grid": torch.empty((v * n * 2,), dtype=torch.float32, device=dev) if want_grid else None,
          "mask": torch.empty((v * n,), dtype=torch.uint8, device=dev) if want_grid else None}
-    n_valid_dev = torch.empty((1 + b + int(extra_words),), dtype=torch.int32, device=dev)
-    ws_bytes = lib.eprecon_back_project_workspace_bytes(n, b, v, c, h, w, layout)
-    ws = _lib.workspace(ws_bytes, dev)
-    rc = lib.eprecon_back_project_async(
-        _lib.ptr(coords_i), n, _lib.ptr(origin_f), b, float(voxel_size), _lib.ptr(feats_c), layout,
-        _lib.ptr(krcam_f), v, c, h, w, int(min_view), mode, _lib.ptr(t["feats"]), _lib.ptr(t["mean"]),
-        _lib.ptr(t["coords"]), _lib.ptr(t["count"]), _lib.ptr(t["grid"]), _lib.ptr(t["mask"]),
-        _lib.ptr(n_valid_dev), _lib.ptr(ws), ws.numel(), _lib.current_stream())
-    _lib.check(rc, "eprecon_back_project_async")
+    if counted is not None:
+        n_valid_dev, ws = counted.n_valid_dev, counted.ws
+        if counted.stream is not None:
+            torch.cuda.current_stream(dev).wait_stream(counted.stream)
+    else:
+        n_valid_dev = torch.empty((1 + b + int(extra_words),), dtype=torch.int32, device=dev)
+        ws_bytes = lib.eprecon_back_project_workspace_bytes(n, b, v, c, h, w, layout)
+        ws = _lib.workspace(ws_bytes, dev)
+    _arm_rank(lib, rank_out, n, b)
+    tail = (_lib.ptr(coords_i), n, _lib.ptr(origin_f), b, float(voxel_size), _lib.ptr(feats_c), layout,
+            _lib.ptr(krcam_f), v, c, h, w, int(min_view), mode, _lib.ptr(t["feats"]), _lib.ptr(t["mean"]),
+            _lib.ptr(t["coords"]), _lib.ptr(t["count"]), _lib.ptr(t["grid"]), _lib.ptr(t["mask"]),
+            _lib.ptr(n_valid_dev), _lib.ptr(ws), ws.numel(), _lib.current_stream())
+    if counted is not None:
+        _lib.check(lib.eprecon_back_project_phase_async(2, *tail), "eprecon_back_project_phase_async")
+    else:
+        _lib.check(lib.eprecon_back_project_async(*tail), "eprecon_back_project_async")
     read = None if hold_read else _lib.PinnedRead(n_valid_dev[:1 + b])
     # inputs stay referenced until result(): the kernels may still be reading them
-    t["_keep"] = (coords_i, origin_f, krcam_f, feats_c, n_valid_dev)
+    t["_keep"] = (coords_i, origin_f, krcam_f, feats_c, n_valid_dev, ws if counted is not None else None)
     pend = PendingBackProject(t, n, v, c, b, int(min_valid_per_batch), read, want_grid, want_mean)
     pend.n_valid_dev, pend.coords_all = n_valid_dev, t["coords"]
     return pend
 
 
 def run(coords, origin, voxel_size, feats, krcam, min_view, mode=MODE_MEAN, min_valid_per_batch=1,
-        want_grid=False, want_mean=False):
+        want_grid=False, want_mean=False, rank_out=None):
     """Low-level entry: returns None (reference: `return None`) or a dict of device tensors
     {feats [n_valid, C(+1)], coords int32 [n_valid, 4], count f32 [N], n_valid, (grid, mask, mean)}."""
     lib = _lib.load()
@@ -143,6 +218,7 @@ def run(coords, origin, voxel_size, feats, krcam, min_view, mode=MODE_MEAN, min_
         # every voxel is valid (the view count is never negative; the one batch element owns all rows): nothing to wait for.
         # The count is still produced on the device and checked with the level's next blocking read (a batch index out of
         # range is the one way a row can drop out).
+        _arm_rank(lib, rank_out, n, b)
         _lib.check(lib.eprecon_back_project_async(
             _lib.ptr(coords_i), n, _lib.ptr(origin_f), b, float(voxel_size), _lib.ptr(feats_c), layout,
             _lib.ptr(krcam_f), v, c, h, w, int(min_view), mode, _lib.ptr(out_feats), _lib.ptr(out_mean), _lib.ptr(out_coords),
@@ -157,6 +233,7 @@ def run(coords, origin, voxel_size, feats, krcam, min_view, mode=MODE_MEAN, min_
             res["mean"] = out_mean
         return res
     _lib.count_host_read()
+    _arm_rank(lib, rank_out, n, b)
     rc = lib.eprecon_back_project(
         _lib.ptr(coords_i), n, _lib.ptr(origin_f), b, float(voxel_size), _lib.ptr(feats_c), layout,
         _lib.ptr(krcam_f), v, c, h, w, int(min_view), mode, int(min_valid_per_batch),
@@ -238,7 +315,7 @@ def forward_behind(module, coords, origin, voxel_size, feats, KRcam, min_view_nu
     return [res["feats"], out_coords, res.get("grid"), res.get("mask"), res["count"]], finish(res["n_valid"], host[nb:])
 
 
-def view_variance(coords, origin, voxel_size, feats_fused, KRcam, min_view_number, min_valid=1000):
+def view_variance(coords, origin, voxel_size, feats_fused, KRcam, min_view_number, min_valid=1000, rank_out=None):
     """Per-voxel population variance over the visible views of the fused 32-channel maps
     (models/occupancy_initialization.py:79-128).  Returns None when fewer than `min_valid` voxels
     are valid (:107-108), else dict(var, mean, coords, count, n_valid)."""
@@ -248,7 +325,7 @@ def view_variance(coords, origin, voxel_size, feats_fused, KRcam, min_view_numbe
                               min_valid_per_batch=min_valid, want_mean=True)
     else:
         res = run(coords, origin, voxel_size, feats_fused, KRcam, min_view_number, MODE_VARIANCE,
-                  min_valid_per_batch=min_valid, want_mean=True)
+                  min_valid_per_batch=min_valid, want_mean=True, rank_out=rank_out)
     if res is None:
         return None
     res["var"] = res.pop("feats")

@@ -73,6 +73,7 @@ struct BpParams {
     const int32_t *blk_batch;  // [nblk_count][batch] per-batch valid counts of the count workgroups (batch > 1), else null
     int nblk_count;
     int xcd_slabs;  // 1 (default): every XCD walks one contiguous range of tiles (ep::xcd_remap); 0: tile = hardware block id
+    int32_t *rank;  // [n + 1] or null: list entry -> output row or -1, then one word 0 (eprecon_back_project_rank_out)
 };
 
 struct Proj {
@@ -363,6 +364,16 @@ __device__ __forceinline__ TileBase tile_base_finish(const BpParams &p, int lb, 
     return r;
 }
 
+// The rank volume of a list that IS the x-major raster of a dense grid (list entry e = cell e; back_project.mark_dense): the
+// gather has just given every entry of its tile an output row or none, which is what eprecon_grid_rank_async would recompute
+// from the compacted coordinates with two clears and a scatter.  Every entry of every tile is written (tiles without a valid
+// voxel too: before their early return); the workgroup of the last tile adds the trailing "not on the grid" word, 0 here.
+__device__ __forceinline__ void gather_rank_store(const BpParams &p, int lb, int e, bool mine, bool valid, int orow)
+{
+    if (mine) p.rank[e] = valid ? orow : -1;
+    if (lb == (int)gridDim.x - 1 && threadIdx.x == 0) p.rank[p.n] = 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // K2 + K3 (+K4): compaction and bilinear gather
 // ---------------------------------------------------------------------------------------------
@@ -505,8 +516,9 @@ __global__ __launch_bounds__(256) void bp_gather_kernel(BpParams p)
     const int rank = block_exclusive_rank<BLOCK>(valid, sWave, nloc);
     TileBase tb = {0, 0};
     if (p.fold) tb = tile_base_finish(p, lb, sFold);
-    if (nloc == 0) return;
     const int base = p.fold ? tb.base : p.block_offsets[lb];
+    if (p.rank) gather_rank_store(p, lb, e, tid < VOX && e < p.n, valid, base + rank);
+    if (nloc == 0) return;
     const int n_valid = p.fold ? tb.n_valid : p.n_valid_dev[0];
     const int cout = (MODE == EPRECON_BP_MEAN_DEPTH) ? p.C + 1 : p.C;
     if (valid) {
@@ -692,11 +704,12 @@ __global__ __launch_bounds__(256) void bp_gather_mlp_kernel(BpParams p)
     const int rank = block_exclusive_rank<BLOCK>(valid, sWave, nloc);
     TileBase tb = {0, 0};
     if (p.fold) tb = tile_base_finish(p, lb, sFold);
+    const int o = (p.fold ? tb.base : p.block_offsets[lb]) + rank;
+    if (p.rank) gather_rank_store(p, lb, e, tid < VOX && e < p.n, valid, o);
     if (nloc == 0) return;
     const int n_valid = p.fold ? tb.n_valid : p.n_valid_dev[0];
     const int cout = (MODE == EPRECON_BP_MEAN_DEPTH) ? p.C + 1 : p.C;
     if (valid) {
-        const int o = (p.fold ? tb.base : p.block_offsets[lb]) + rank;
         sSlot[rank] = tid;
         sOut[tid] = o;
         if (VPT == 1) sVis[tid] = vis;
@@ -1206,20 +1219,44 @@ int eprecon_views_to_rows_async(const eprecon_views_desc *desc, void *stream)
     return EPRECON_OK;
 }
 
-int eprecon_back_project_async(const int32_t *coords, int64_t n, const float *origin, int batch,
-                               float voxel_size, const float *feats, int feats_layout,
-                               const float *krcam, int n_views, int channels, int height,
-                               int width, int min_view, int mode, float *out_feats,
-                               float *out_mean, int32_t *out_coords, float *count,
-                               float *out_grid, uint8_t *out_mask, int32_t *n_valid_dev,
-                               void *workspace, size_t workspace_bytes, void *stream)
+// One-shot, per host thread: the NEXT eprecon_back_project_async / eprecon_back_project call of this thread also writes
+// rank int32[n + 1] (BpParams::rank).  The call takes the pointer whatever it returns, so it never reaches a later call.
+static thread_local int32_t *t_rank_out = nullptr;
+
+int eprecon_back_project_rank_out(int32_t *rank)
+{
+    t_rank_out = rank;
+    return EPRECON_OK;
+}
+
+int eprecon_init_glue(void) { return ep::switch_off("EPRECON_INIT_GLUE") ? 0 : 1; }
+
+// The call in two halves for channels-last maps (EPRECON_BP_COUNT / EPRECON_BP_GATHER; 0: the whole call).  The count half --
+// visible views per voxel, tile totals, and the scan launch where the gather does not fold it in -- reads coordinates and
+// matrices only, so a caller may queue it on another stream while the maps are still being computed; the gather half then
+// needs the same arguments, the same workspace, and the count half finished.
+static int bp_async_impl(int phase, const int32_t *coords, int64_t n, const float *origin, int batch,
+                         float voxel_size, const float *feats, int feats_layout,
+                         const float *krcam, int n_views, int channels, int height,
+                         int width, int min_view, int mode, float *out_feats,
+                         float *out_mean, int32_t *out_coords, float *count,
+                         float *out_grid, uint8_t *out_mask, int32_t *n_valid_dev,
+                         void *workspace, size_t workspace_bytes, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
+    int32_t *rank_out = nullptr;
+    if (phase != EPRECON_BP_COUNT) {      // (the count half writes no rows: the pointer waits for the gather half)
+        rank_out = t_rank_out;
+        t_rank_out = nullptr;
+    }
+    if (rank_out && batch != 1) return EPRECON_ERR_ARG;      // (the rows of several batch elements interleave: no single raster)
+    if (phase != 0 && feats_layout != EPRECON_LAYOUT_NHWC) return EPRECON_ERR_ARG;    // (NCHW: re-layout and count are one grid)
+    if (phase == EPRECON_BP_COUNT && !feats) feats = reinterpret_cast<const float *>(krcam);   // (not read by this half)
     if (n < 0 || n > 0x7fffffff / 64 || batch <= 0 || n_views <= 0 || n_views > 32 || channels <= 0 ||
         height <= 1 || width <= 1 || mode < 0 || mode > 2)
         return EPRECON_ERR_ARG;
     if (!origin || !feats || !krcam || !n_valid_dev || !workspace) return EPRECON_ERR_ARG;
-    if (n > 0 && (!coords || !out_feats || !out_coords || !count)) return EPRECON_ERR_ARG;
+    if (n > 0 && (!coords || !count || (phase != EPRECON_BP_COUNT && (!out_feats || !out_coords)))) return EPRECON_ERR_ARG;
     if ((size_t)n_views * batch * 12 * sizeof(float) > 32 * 1024) return EPRECON_ERR_UNSUPPORTED;
     if (workspace_bytes < eprecon_back_project_workspace_bytes(n, batch, n_views, channels, height,
                                                                width, feats_layout))
@@ -1241,8 +1278,9 @@ int eprecon_back_project_async(const int32_t *coords, int64_t n, const float *or
     // the empty list needs them cleared.  (The four-launch chain clears them as it always did: inside the re-layout launch when
     // there is one -- NCHW features, <= 255 batch elements -- else by a memset.)
     const bool clear_in_relayout = chain4 && n > 0 && nchw && batch < 256;
-    if (n == 0 || (chain4 && !clear_in_relayout))
+    if ((n == 0 || (chain4 && !clear_in_relayout)) && phase != EPRECON_BP_GATHER)
         EP_HIP_CHECK(hipMemsetAsync(n_valid_dev, 0, sizeof(int32_t) * (size_t)(1 + batch), st));
+    if (n == 0 && rank_out) EP_HIP_CHECK(hipMemsetAsync(rank_out, 0, sizeof(int32_t), st));
     if (n == 0) return EPRECON_OK;
 
     char *ws = reinterpret_cast<char *>(workspace);
@@ -1261,6 +1299,7 @@ int eprecon_back_project_async(const int32_t *coords, int64_t n, const float *or
     p.min_view = min_view; p.out_feats = out_feats; p.out_mean = out_mean; p.out_coords = out_coords;
     p.count = count; p.out_grid = out_grid; p.out_mask = out_mask; p.n_valid_dev = n_valid_dev;
     p.block_offsets = block_sums;
+    p.rank = rank_out;
     {   // EPRECON_BP_XCD_SLABS=0 (read per call): the gather's tiles in hardware block order — round-robin over the eight XCDs, so
         // every XCD's L2 sees tiles from the whole volume — instead of one contiguous slab of the raster per XCD.  Same results.
         const char *e = getenv("EPRECON_BP_XCD_SLABS");
@@ -1296,7 +1335,7 @@ int eprecon_back_project_async(const int32_t *coords, int64_t n, const float *or
         else { EP_PREPARE(16); }
 #undef EP_PREPARE
         EP_LAUNCH_CHECK();
-    } else {
+    } else if (phase != EPRECON_BP_GATHER) {
         if (nchw) {   // (only the four-launch chain comes here with NCHW maps; it clears the counters on the way for batch < 256)
             hipLaunchKernelGGL(nchw_to_nhwc_kernel<false>, dim3((unsigned)ep::ceil_div(height * width, kTrPix), (unsigned)(n_views * batch)),
                                dim3(256), lds_t, st, feats, tmp, channels, height * width, pix_stride,
@@ -1311,11 +1350,12 @@ int eprecon_back_project_async(const int32_t *coords, int64_t n, const float *or
             hipLaunchKernelGGL((bp_count_kernel<16>), dim3(nblk_count), dim3(256), lds_count, st, p, block_sums, bb);
         EP_LAUNCH_CHECK();
     }
-    if (!p.fold) {
+    if (!p.fold && phase != EPRECON_BP_GATHER) {
         hipLaunchKernelGGL(bp_scan_kernel, dim3(1), dim3(1024), 0, st, block_sums, ntile, n_valid_dev,
                            (const int32_t *)bb, nblk_count, batch);
         EP_LAUNCH_CHECK();
     }
+    if (phase == EPRECON_BP_COUNT) return EPRECON_OK;
 
     const bool prof = g_prof.on && g_prof.start;
     if (prof) EP_HIP_CHECK(hipEventRecord(g_prof.start, st));
@@ -1351,6 +1391,33 @@ int eprecon_back_project_async(const int32_t *coords, int64_t n, const float *or
         EP_LAUNCH_CHECK();
     }
     return EPRECON_OK;
+}
+
+int eprecon_back_project_async(const int32_t *coords, int64_t n, const float *origin, int batch,
+                               float voxel_size, const float *feats, int feats_layout,
+                               const float *krcam, int n_views, int channels, int height,
+                               int width, int min_view, int mode, float *out_feats,
+                               float *out_mean, int32_t *out_coords, float *count,
+                               float *out_grid, uint8_t *out_mask, int32_t *n_valid_dev,
+                               void *workspace, size_t workspace_bytes, void *stream)
+{
+    return bp_async_impl(0, coords, n, origin, batch, voxel_size, feats, feats_layout, krcam, n_views, channels, height, width,
+                         min_view, mode, out_feats, out_mean, out_coords, count, out_grid, out_mask, n_valid_dev, workspace,
+                         workspace_bytes, stream);
+}
+
+int eprecon_back_project_phase_async(int phase, const int32_t *coords, int64_t n, const float *origin, int batch,
+                                     float voxel_size, const float *feats, int feats_layout,
+                                     const float *krcam, int n_views, int channels, int height,
+                                     int width, int min_view, int mode, float *out_feats,
+                                     float *out_mean, int32_t *out_coords, float *count,
+                                     float *out_grid, uint8_t *out_mask, int32_t *n_valid_dev,
+                                     void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (phase != EPRECON_BP_COUNT && phase != EPRECON_BP_GATHER) return EPRECON_ERR_ARG;
+    return bp_async_impl(phase, coords, n, origin, batch, voxel_size, feats, feats_layout, krcam, n_views, channels, height, width,
+                         min_view, mode, out_feats, out_mean, out_coords, count, out_grid, out_mask, n_valid_dev, workspace,
+                         workspace_bytes, stream);
 }
 
 int eprecon_back_project(const int32_t *coords, int64_t n, const float *origin, int batch,

@@ -28,6 +28,29 @@ __global__ __launch_bounds__(256) void init_mark_kernel(const float *logit, cons
     }
 }
 
+// The same marks for a set that lives on a dense grid whose rank volume (cell -> row or -1, eprecon_grid_rank_async) exists
+// already: one thread per COARSE cell ORs init_mark_kernel's comparison over its `ratio`^3 fine cells and stores 0 or 1, so every
+// byte of the volume is written by this launch and nothing has to be cleared in front of it.
+__global__ __launch_bounds__(256) void init_mark_dense_kernel(const float *logit, int n, const int32_t *rank, int gx, int gy, int gz,
+                                                              int ratio, float thr, int D, unsigned char *marks)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= D * D * D) return;
+    const int z = i % D, y = (i / D) % D, x = i / (D * D);
+    bool hit = false;
+    for (int dx = 0; dx < ratio; ++dx)
+        for (int dy = 0; dy < ratio; ++dy)
+            for (int dz = 0; dz < ratio; ++dz) {
+                const int fx = x * ratio + dx, fy = y * ratio + dy, fz = z * ratio + dz;
+                if (fx >= gx || fy >= gy || fz >= gz) continue;
+                const int r = rank[((size_t)fx * gy + fy) * gz + fz];
+                if (r < 0 || r >= n) continue;
+                const float sig = 1.0f / (1.0f + expf(-logit[r]));
+                hit = hit || sig > thr;
+            }
+    marks[i] = hit ? 1 : 0;
+}
+
 // Morphology on bit columns: the D (<= 32) cells of one (x, y) column are one 32-bit word, bit z.
 // A zero-padded 3^3 box erosion is AND over the 9 neighbour columns of (w & w<<1 & w>>1); the
 // dilation is the same with OR.  One thread per column; the whole volume is D*D words in LDS.
@@ -154,6 +177,32 @@ int eprecon_init_select_async(const float *logit, const int32_t *coords, int64_t
     }
     hipLaunchKernelGGL(init_select_kernel, dim3(1), dim3(kSelThreads), 0, st, (const unsigned char *)marks, batch,
                        dim, cell, reinterpret_cast<int4 *>(out_coords), n_out_dev);
+    EP_LAUNCH_CHECK();
+    return EPRECON_OK;
+}
+
+// eprecon_init_select_async for ONE batch element whose voxels are rows of a dense grid_x x grid_y x grid_z grid of `stride`
+// voxels (cell % stride == 0) with its rank volume at hand: the marks come from one launch over the coarse cells through
+// `rank`, with no clear and no pass over the list (same coordinates, counts and order).  EPRECON_INIT_GLUE=0: the list form.
+int eprecon_init_select_dense_async(const float *logit, const int32_t *coords, int64_t n, const int32_t *rank, int grid_x,
+                                    int grid_y, int grid_z, int stride, float threshold, int dim, int cell, int32_t *out_coords,
+                                    int32_t *n_out_dev, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (n < 0 || n > 0x7fffffff || dim <= 0 || dim > 32 || cell <= 0 || stride <= 0 || cell % stride || grid_x <= 0 || grid_y <= 0 ||
+        grid_z <= 0 || (int64_t)grid_x * grid_y * grid_z > 0x7ffffff0 || !rank || !out_coords || !n_out_dev || !workspace ||
+        (n > 0 && (!logit || !coords)))
+        return EPRECON_ERR_ARG;
+    if (switch_off("EPRECON_INIT_GLUE"))
+        return eprecon_init_select_async(logit, coords, n, threshold, 1, dim, cell, out_coords, n_out_dev, workspace, workspace_bytes,
+                                         stream);
+    if (workspace_bytes < eprecon_init_select_workspace_bytes(1, dim)) return EPRECON_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned char *marks = reinterpret_cast<unsigned char *>(workspace);
+    hipLaunchKernelGGL(init_mark_dense_kernel, dim3((unsigned)ceil_div(dim * dim * dim, 256)), dim3(256), 0, st, logit, (int)n, rank,
+                       grid_x, grid_y, grid_z, cell / stride, threshold, dim, marks);
+    EP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(init_select_kernel, dim3(1), dim3(kSelThreads), 0, st, (const unsigned char *)marks, 1, dim, cell,
+                       reinterpret_cast<int4 *>(out_coords), n_out_dev);
     EP_LAUNCH_CHECK();
     return EPRECON_OK;
 }

@@ -258,6 +258,87 @@ __global__ __launch_bounds__(256) void affine_rows_kernel(const float *x, int n,
     out[(size_t)r * ld_out + c] = v;
 }
 
+// The two joins of the 2D fusion stack (Occupancy_Initialization.feat_fusion_pre): the outer levels reach the 1/8 grid through a
+// 2x2 mean (1/4 level) or a bilinear x2 (1/16 level) and land in their channel slice of the concat buffer.  One launch each from
+// the level's raw rows and its pending BatchNorm, instead of affine_rows -> a resampling launch -> a strided copy with two
+// intermediate tensors: t = [relu](x * scale + shift) is formed on load (affine_rows_kernel's expression), then
+//   pool   (((0 + t00) + t01) + t10) + t11) / 4: the sum in (kh, kw) order from zero, then the divide, as the library's
+//          average pooling of a channels-last tensor does it; odd heights / widths drop their last row / column
+//   up     upsample2x_nhwc_kernel's taps, weights and sum (csrc/grid_ops.hip)
+// VEC = 4: four channels per thread where C, the strides and the pointers allow 16-byte accesses; else one.
+template <int VEC>
+__device__ __forceinline__ void load_affine(const float *x, const float *scale, const float *shift, int relu, float (&t)[VEC])
+{
+    if constexpr (VEC == 4) {
+        const float4 v = *reinterpret_cast<const float4 *>(x);
+        t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
+    } else {
+        t[0] = x[0];
+    }
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        t[k] = fmaf(t[k], scale[k], shift[k]);
+        if (relu) t[k] = fmaxf(t[k], 0.0f);
+    }
+}
+
+template <int VEC>
+__device__ __forceinline__ void store_vec(float *dst, const float (&o)[VEC])
+{
+    if constexpr (VEC == 4) *reinterpret_cast<float4 *>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+    else dst[0] = o[0];
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void affine_pool2_rows_kernel(const float *x, int maps, int h, int w, int C, int ld_x,
+                                                                const float *scale, const float *shift, int relu, float *out,
+                                                                int ld_out)
+{
+    const int cv = C / VEC, oh = h / 2, ow = w / 2;
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)maps * oh * ow * cv) return;
+    const int c = (int)(e % cv) * VEC;
+    const size_t orow = e / cv;
+    const int ox = (int)(orow % ow), oy = (int)((orow / ow) % oh), img = (int)(orow / ow / oh);
+    const float *p = x + (((size_t)img * h + 2 * oy) * w + 2 * ox) * ld_x + c;
+    float t00[VEC], t01[VEC], t10[VEC], t11[VEC], o[VEC];
+    load_affine<VEC>(p, scale + c, shift + c, relu, t00);
+    load_affine<VEC>(p + ld_x, scale + c, shift + c, relu, t01);
+    load_affine<VEC>(p + (size_t)w * ld_x, scale + c, shift + c, relu, t10);
+    load_affine<VEC>(p + (size_t)(w + 1) * ld_x, scale + c, shift + c, relu, t11);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) o[k] = ((((0.0f + t00[k]) + t01[k]) + t10[k]) + t11[k]) / 4.0f;
+    store_vec<VEC>(out + orow * ld_out + c, o);
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void affine_up2_rows_kernel(const float *x, int maps, int h, int w, int C, int ld_x,
+                                                              const float *scale, const float *shift, int relu, float *out,
+                                                              int ld_out)
+{
+    const int cv = C / VEC;
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)maps * 4 * h * w * cv) return;
+    const int c = (int)(e % cv) * VEC;
+    const size_t orow = e / cv;
+    const int ox = (int)(orow % (2 * w)), oy = (int)((orow / (2 * w)) % (2 * h)), img = (int)(orow / (2 * w) / (2 * h));
+    const float sx = fmaxf(((float)ox + 0.5f) * 0.5f - 0.5f, 0.0f);
+    const float sy = fmaxf(((float)oy + 0.5f) * 0.5f - 0.5f, 0.0f);
+    const int x0 = (int)sx, y0 = (int)sy;
+    const int x1 = min(x0 + 1, w - 1), y1 = min(y0 + 1, h - 1);
+    const float lx = sx - (float)x0, ly = sy - (float)y0;
+    const float *base = x + (size_t)img * h * w * ld_x + c;
+    float a[VEC], b[VEC], d[VEC], f[VEC], o[VEC];
+    load_affine<VEC>(base + ((size_t)y0 * w + x0) * ld_x, scale + c, shift + c, relu, a);
+    load_affine<VEC>(base + ((size_t)y0 * w + x1) * ld_x, scale + c, shift + c, relu, b);
+    load_affine<VEC>(base + ((size_t)y1 * w + x0) * ld_x, scale + c, shift + c, relu, d);
+    load_affine<VEC>(base + ((size_t)y1 * w + x1) * ld_x, scale + c, shift + c, relu, f);
+    const float w00 = (1.0f - ly) * (1.0f - lx), w01 = (1.0f - ly) * lx, w10 = ly * (1.0f - lx), w11 = ly * lx;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) o[k] = w00 * a[k] + w01 * b[k] + w10 * d[k] + w11 * f[k];
+    store_vec<VEC>(out + orow * ld_out + c, o);
+}
+
 // BatchNorm form (c) (csrc/conv_common.hpp): the accumulator block of a producer -> (scale, shift) vectors — the stand-alone
 // finish for consumers that do not do it in their prologue (dense-grid tile kernels, residual operands)
 __global__ __launch_bounds__(256) void bn_acc_affine_kernel(const long long *acc, int ld, int c0, int C, float eps, float *scale,
@@ -310,11 +391,89 @@ __global__ __launch_bounds__(256) void affine_rows_res_kernel(const float *x, in
 // 64 channels x 256 rows, the list merged once per workgroup by four row lanes with eight summary rows in flight — lost as well:
 // SPVCNN of the coarsest level 1.42 -> 1.68 ms.  The merge is a chain of dependent divisions; 74 workgroups repeating it in
 // front of their rows is slower than one 5 us launch doing it once.)
+//
+// The exception is a handful of channels (C <= kBnMergeApplyMaxC: the single-channel BatchNorm of the occupancy logit, 864
+// summaries x 3 floats = 10 KB): there the merge is 4 row merges per thread and one pass of the tree, and the finalize launch it
+// replaces (5.5 us + a dependent boundary) is as long as the apply launch itself.  bn_merge_apply_kernel does bn_finalize_kernel's
+// merges in bn_finalize_kernel's order — rows t, t + 256, ... per thread, then the tree (t, t + 128), (t, t + 64), ... (0, 1) with
+// the lower index on the left — so mean and variance have the bits of the two-launch form: the levels 128 and 64 out of LDS by
+// wave 0, the levels 32 .. 1 as down-shuffles inside it (lane t takes lane t + s; what the lanes >= s compute is never read).
+// The rows are then normalised with bn_apply_kernel's expression.  EPRECON_INIT_GLUE=0: the two launches.
+constexpr int kBnMergeApplyMaxC = 4;
+constexpr int kBnMergeApplyBlocks = 256;    // workgroups at most: one per CU, the rows in grid strides
+
+template <int NU>
+__global__ __launch_bounds__(256) void bn_merge_apply_kernel(const float *x, int n, int C, int ld_x, const float *partial, int nblk,
+                                                             int64_t ld, const float *gamma, const float *beta, float eps,
+                                                             const float *res, int ld_res, const float *res_scale,
+                                                             const float *res_shift, int relu, float *out, int ld_out,
+                                                             float *mean_out, float *var_out)
+{
+    __shared__ float sN[256], sMean[256], sM2[256];
+    __shared__ float sStat[2 * kBnMergeApplyMaxC];
+    const int tid = threadIdx.x;
+    for (int c = 0; c < C; ++c) {
+        float a_n = 0.0f, a_mean = 0.0f, a_m2 = 0.0f;
+        bn_merge_rows<NU>(partial, nblk, ld, C, c, tid, a_n, a_mean, a_m2);
+        sN[tid] = a_n; sMean[tid] = a_mean; sM2[tid] = a_m2;
+        __syncthreads();
+        if (tid < 64) {
+            chan_merge(a_n, a_mean, a_m2, sN[tid + 128], sMean[tid + 128], sM2[tid + 128]);
+            float b_n = sN[tid + 64], b_mean = sMean[tid + 64], b_m2 = sM2[tid + 64];
+            chan_merge(b_n, b_mean, b_m2, sN[tid + 192], sMean[tid + 192], sM2[tid + 192]);
+            chan_merge(a_n, a_mean, a_m2, b_n, b_mean, b_m2);
+#pragma unroll
+            for (int s = 32; s > 0; s >>= 1) {
+                const float on = __shfl_down(a_n, s), om = __shfl_down(a_mean, s), oq = __shfl_down(a_m2, s);
+                chan_merge(a_n, a_mean, a_m2, on, om, oq);
+            }
+            if (tid == 0) {
+                sStat[c] = a_mean;
+                sStat[kBnMergeApplyMaxC + c] = a_n > 0.0f ? a_m2 / a_n : 0.0f;  // biased variance
+            }
+        }
+        __syncthreads();
+    }
+    if (blockIdx.x == 0 && tid < C) {
+        if (mean_out) mean_out[tid] = sStat[tid];
+        if (var_out) var_out[tid] = sStat[kBnMergeApplyMaxC + tid];
+    }
+    const size_t total = (size_t)n * C;
+    for (size_t e = (size_t)blockIdx.x * 256 + tid; e < total; e += (size_t)gridDim.x * 256) {
+        const int r = (int)(e / C), c = (int)(e - (size_t)r * C);
+        const float inv = 1.0f / sqrtf(sStat[kBnMergeApplyMaxC + c] + eps);
+        float v = (x[(size_t)r * ld_x + c] - sStat[c]) * inv;
+        v = v * (gamma ? gamma[c] : 1.0f) + (beta ? beta[c] : 0.0f);
+        if (res) {
+            float rv = res[(size_t)r * ld_res + c];
+            if (res_scale) rv = fmaf(rv, res_scale[c], res_shift[c]);
+            v += rv;
+        }
+        if (relu) v = fmaxf(v, 0.0f);
+        out[(size_t)r * ld_out + c] = v;
+    }
+}
+
 int bn_finalize_apply(const float *x, int64_t n, int channels, int ld_x, const float *partial, int nblk, int64_t ld,
                       const float *gamma, const float *beta, float eps, const float *residual, int ld_res,
                       int relu, float *out, int ld_out, float *mean, float *var, hipStream_t st,
                       const float *res_scale = nullptr, const float *res_shift = nullptr)
 {
+    if (channels <= kBnMergeApplyMaxC && !switch_off("EPRECON_INIT_GLUE")) {
+        const unsigned blocks = (unsigned)ceil_div(n * channels, (int64_t)256);
+        const dim3 grid(blocks < (unsigned)kBnMergeApplyBlocks ? blocks : (unsigned)kBnMergeApplyBlocks);
+        switch (bn_finalize_nu(nblk)) {
+#define EP_MERGE_APPLY(NU)                                                                                                       \
+    case NU:                                                                                                                     \
+        hipLaunchKernelGGL(bn_merge_apply_kernel<NU>, grid, dim3(256), 0, st, x, (int)n, channels, ld_x, partial, nblk, ld, gamma, \
+                           beta, eps, residual, ld_res, res_scale, res_shift, relu, out, ld_out, mean, var);                      \
+        break
+            EP_MERGE_APPLY(1); EP_MERGE_APPLY(2); EP_MERGE_APPLY(4); EP_MERGE_APPLY(8); EP_MERGE_APPLY(16);
+#undef EP_MERGE_APPLY
+        }
+        EP_LAUNCH_CHECK();
+        return EPRECON_OK;
+    }
     switch (bn_finalize_nu(nblk)) {
 #define EP_FINALIZE(NU) \
     case NU: hipLaunchKernelGGL(bn_finalize_kernel<NU>, dim3(channels), dim3(256), 0, st, partial, nblk, ld, channels, mean, var); break
@@ -444,6 +603,49 @@ int eprecon_affine_rows_async(const float *x, int64_t n, int channels, int ld_x,
     if (n == 0) return EPRECON_OK;
     hipLaunchKernelGGL(affine_rows_kernel, dim3((unsigned)ceil_div(n * channels, (int64_t)256)), dim3(256), 0,
                        (hipStream_t)stream, x, (int)n, channels, ld_x, scale, shift, relu, out, ld_out);
+    EP_LAUNCH_CHECK();
+    return EPRECON_OK;
+}
+
+static bool rows_vec4(const float *x, int ld_x, const float *out, int ld_out, int channels)
+{
+    return channels % 4 == 0 && ld_x % 4 == 0 && ld_out % 4 == 0 && ((uintptr_t)x | (uintptr_t)out) % 16 == 0;
+}
+
+int eprecon_affine_pool2_rows_async(const float *x, int maps, int height, int width, int channels, int ld_x, const float *scale,
+                                    const float *shift, int relu, float *out, int ld_out, void *stream)
+{
+    if (!x || !out || !scale || !shift || maps <= 0 || height < 2 || width < 2 || channels <= 0 || ld_x < channels ||
+        ld_out < channels || (int64_t)maps * height * width * channels > 0x7fffffffll)
+        return EPRECON_ERR_ARG;
+    const bool v4 = rows_vec4(x, ld_x, out, ld_out, channels);
+    const int64_t total = (int64_t)maps * (height / 2) * (width / 2) * (channels / (v4 ? 4 : 1));
+    const dim3 grid((unsigned)ceil_div(total, (int64_t)256));
+    if (v4)
+        hipLaunchKernelGGL(affine_pool2_rows_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, x, maps, height, width, channels,
+                           ld_x, scale, shift, relu, out, ld_out);
+    else
+        hipLaunchKernelGGL(affine_pool2_rows_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, maps, height, width, channels,
+                           ld_x, scale, shift, relu, out, ld_out);
+    EP_LAUNCH_CHECK();
+    return EPRECON_OK;
+}
+
+int eprecon_affine_up2_rows_async(const float *x, int maps, int height, int width, int channels, int ld_x, const float *scale,
+                                  const float *shift, int relu, float *out, int ld_out, void *stream)
+{
+    if (!x || !out || !scale || !shift || maps <= 0 || height <= 0 || width <= 0 || channels <= 0 || ld_x < channels ||
+        ld_out < channels || (int64_t)maps * height * width * 4 * channels > 0x7fffffffll)
+        return EPRECON_ERR_ARG;
+    const bool v4 = rows_vec4(x, ld_x, out, ld_out, channels);
+    const int64_t total = (int64_t)maps * 4 * height * width * (channels / (v4 ? 4 : 1));
+    const dim3 grid((unsigned)ceil_div(total, (int64_t)256));
+    if (v4)
+        hipLaunchKernelGGL(affine_up2_rows_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, x, maps, height, width, channels,
+                           ld_x, scale, shift, relu, out, ld_out);
+    else
+        hipLaunchKernelGGL(affine_up2_rows_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, maps, height, width, channels,
+                           ld_x, scale, shift, relu, out, ld_out);
     EP_LAUNCH_CHECK();
     return EPRECON_OK;
 }

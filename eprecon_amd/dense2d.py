@@ -287,6 +287,28 @@ def materialize(act, out=None):
     return out
 
 
+def _join_rows(name, act, grid, out, out_rows):
+    rows = act.rows
+    n, c = rows.shape
+    assert n == grid.n and act.scale is not None and out.shape == (out_rows, c) and out.stride(1) == 1 and rows.stride(1) == 1
+    fn = getattr(_lib.load(), name)
+    _lib.check(fn(rows.data_ptr(), grid.maps, grid.height, grid.width, c, rows.stride(0), act.scale.data_ptr(), act.shift.data_ptr(),
+                  int(act.relu), out.data_ptr(), out.stride(0), _lib.current_stream()), name)
+    return out
+
+
+def affine_pool2_rows(act, grid, out):
+    """the pending BatchNorm (+ReLU) of `act`, then the 2x2 mean, written into `out` (rows of the half-resolution grid, possibly a
+    channel slice of a concat buffer): one launch, nothing allocated"""
+    return _join_rows("eprecon_affine_pool2_rows_async", act, grid, out, grid.maps * (grid.height // 2) * (grid.width // 2))
+
+
+def affine_up2_rows(act, grid, out):
+    """the pending BatchNorm (+ReLU) of `act`, then the bilinear x2 upsampling, written into `out` (rows of the double-resolution
+    grid): one launch, nothing allocated"""
+    return _join_rows("eprecon_affine_up2_rows_async", act, grid, out, grid.maps * 4 * grid.height * grid.width)
+
+
 def conv_bn(conv, bn, x, grid, out=None, relu=True, pre_relu=False, pre_residual=None):
     """BN( [ReLU](conv(x) + b) [+ pre_residual] ) [ReLU] on plain pixel rows, result materialised"""
     res = Act(pre_residual) if pre_residual is not None else None

@@ -122,7 +122,7 @@ class Cfg2Step:
         out["init"] = init
         select = None
         if init is not None:
-            select = GO.init_select_async(init[0], init[1], 1, dim=self.shape_init[0] // 2, cell=4)
+            select = GO.init_select_async(init[0], init[1], 1, dim=self.shape_init[0] // 2, cell=4, dense=self.init_net.dense_map)
         if side is not main:
             main.wait_stream(side)
         return out, pending, select

@@ -4,12 +4,10 @@ import torch
 from . import _lib
 
 
-def init_select(logit, coords, batch_size, dim=24, cell=4, threshold=0.3, must_be_zero=()):
-    """models/neucon_network.py:264,298-318.  logit f32[N(,1)] and coords int32[N,4] of the valid
-    48^3 voxels -> int32[M,4] stage-0 coordinates (raster order per batch element) and the
-    per-batch counts (one host sync, like the reference's torch.nonzero).
-    must_be_zero: int32 device scalars ([1]-shaped) read back in the SAME host read; a non-zero one raises (the
-    off-grid counters of the dense-grid convolution maps that produced `logit`, sparse.DenseMap)."""
+def _queue_select(logit, coords, batch_size, dim, cell, threshold, dense):
+    """the selection's launches -> (out int32[batch dim^3, 4], counts int32[1 + batch]), both on the device.
+    dense (optional, one batch element): the sparse.DenseMap of the voxel set `coords` — its rank volume stands in for the
+    list when the marks are made (eprecon_init_select_dense_async)"""
     lib = _lib.load()
     logit = logit.reshape(-1).contiguous()
     coords = coords.contiguous()
@@ -18,10 +16,29 @@ def init_select(logit, coords, batch_size, dim=24, cell=4, threshold=0.3, must_b
     out = torch.empty((batch_size * dim ** 3, 4), dtype=torch.int32, device=dev)
     counts = torch.empty(1 + batch_size, dtype=torch.int32, device=dev)      # (init_select_kernel writes every word)
     ws = _lib.workspace(lib.eprecon_init_select_workspace_bytes(batch_size, dim), dev)
-    _lib.check(lib.eprecon_init_select_async(_lib.ptr(logit), _lib.ptr(coords), coords.shape[0],
-                                             float(threshold), batch_size, dim, cell, _lib.ptr(out),
-                                             _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.current_stream()),
-               "eprecon_init_select_async")
+    if dense is not None and batch_size == 1 and cell % dense.vset.stride == 0:
+        assert dense.vset.n == coords.shape[0]
+        gx, gy, gz = dense.dims
+        _lib.check(lib.eprecon_init_select_dense_async(_lib.ptr(logit), _lib.ptr(coords), coords.shape[0], _lib.ptr(dense.rank),
+                                                       gx, gy, gz, dense.vset.stride, float(threshold), dim, cell, _lib.ptr(out),
+                                                       _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.current_stream()),
+                   "eprecon_init_select_dense_async")
+    else:
+        _lib.check(lib.eprecon_init_select_async(_lib.ptr(logit), _lib.ptr(coords), coords.shape[0],
+                                                 float(threshold), batch_size, dim, cell, _lib.ptr(out),
+                                                 _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.current_stream()),
+                   "eprecon_init_select_async")
+    return out, counts
+
+
+def init_select(logit, coords, batch_size, dim=24, cell=4, threshold=0.3, must_be_zero=(), dense=None):
+    """models/neucon_network.py:264,298-318.  logit f32[N(,1)] and coords int32[N,4] of the valid
+    48^3 voxels -> int32[M,4] stage-0 coordinates (raster order per batch element) and the
+    per-batch counts (one host sync, like the reference's torch.nonzero).
+    must_be_zero: int32 device scalars ([1]-shaped) read back in the SAME host read; a non-zero one raises (the
+    off-grid counters of the dense-grid convolution maps that produced `logit`, sparse.DenseMap).
+    dense: the DenseMap of the voxel set when it has one (one batch element): marks through its rank volume, no clear."""
+    out, counts = _queue_select(logit, coords, batch_size, dim, cell, threshold, dense)
     if must_be_zero:
         host = _lib.read_counts(torch.cat([counts] + [t.reshape(1) for t in must_be_zero]))
         if any(host[1 + batch_size:]):
@@ -45,20 +62,9 @@ class PendingSelect:
         return self._out[: host[0]], host[1:]
 
 
-def init_select_async(logit, coords, batch_size, dim=24, cell=4, threshold=0.3):
+def init_select_async(logit, coords, batch_size, dim=24, cell=4, threshold=0.3, dense=None):
     """init_select without the host round trip: -> PendingSelect"""
-    lib = _lib.load()
-    logit = logit.reshape(-1).contiguous()
-    coords = coords.contiguous()
-    assert coords.dtype == torch.int32 and logit.dtype == torch.float32
-    dev = coords.device
-    out = torch.empty((batch_size * dim ** 3, 4), dtype=torch.int32, device=dev)
-    counts = torch.empty(1 + batch_size, dtype=torch.int32, device=dev)      # (init_select_kernel writes every word)
-    ws = _lib.workspace(lib.eprecon_init_select_workspace_bytes(batch_size, dim), dev)
-    _lib.check(lib.eprecon_init_select_async(_lib.ptr(logit), _lib.ptr(coords), coords.shape[0],
-                                             float(threshold), batch_size, dim, cell, _lib.ptr(out),
-                                             _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.current_stream()),
-               "eprecon_init_select_async")
+    out, counts = _queue_select(logit, coords, batch_size, dim, cell, threshold, dense)
     return PendingSelect(out, _lib.PinnedRead(counts))
 
 

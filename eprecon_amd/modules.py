@@ -400,11 +400,15 @@ class Fusion_Block(nn.Module):
         x = bn2d_train(self.bn2, self.conv2(x), relu=True)
         return self.ELAN(x)
 
-    def run_rows(self, x, grid, out=None):
-        """plain rows in, materialised rows out; 9 convolution launches + 1 affine launch"""
+    def run_act(self, x, grid):
+        """plain rows in, the result with its BatchNorm pending out (dense2d.Act); 9 convolution launches"""
         a = D2.conv_bn_act(self.conv1, self.bn1, D2.Act(x), grid, relu=True)
         a = D2.conv_bn_act(self.conv2, self.bn2, a, grid, relu=True)
-        return D2.materialize(self.ELAN.run_act(a, grid), out=out)
+        return self.ELAN.run_act(a, grid)
+
+    def run_rows(self, x, grid, out=None):
+        """plain rows in, materialised rows out; 9 convolution launches + 1 affine launch"""
+        return D2.materialize(self.run_act(x, grid), out=out)
 
 
 def _ln_rows(norm, y, residual=None, pre_relu=False, post_relu=False):

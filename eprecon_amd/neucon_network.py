@@ -156,7 +156,8 @@ class NeuConNet(nn.Module):
         # (the same host read checks that every voxel of the initialisation set was on the dense grid its convolutions ran on)
         selected, _ = GO.init_select(occ_init, coord_init, bs, dim=shape_init[0] // 2 ** INIT_STAGE,
                                      cell=2 ** self.n_scales, threshold=INIT_OCC_THRESHOLD,
-                                     must_be_zero=getattr(self.initialization, "dense_checks", ()))
+                                     must_be_zero=getattr(self.initialization, "dense_checks", ()),
+                                     dense=getattr(self.initialization, "dense_map", None))
         return init_output, selected, shape_init
 
     def _spvcnn_behind(self, level, inputs, children):

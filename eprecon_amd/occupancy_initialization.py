@@ -35,6 +35,7 @@ class Occupancy_Initialization(nn.Module):
         self.self_fusion_1x = Fusion_Block(ch_initialization_all[0])
         self.self_fusion_2x = Fusion_Block(ch_initialization_all[1])
         self.self_fusion_4x = Fusion_Block(ch_initialization_all[2])
+        self.ch_down = d
         self.pool4x = nn.AvgPool2d(2)
         self.fusion_down = Conv2d_Block(ch_all, d, 1)
         self.post_fusion_1 = Conv2d_Residual_Block(d, 3)
@@ -112,12 +113,9 @@ class Occupancy_Initialization(nn.Module):
             s1.wait_stream(main)
             s4.wait_stream(main)
             with torch.cuda.stream(s4):
-                f4 = self.self_fusion_4x.run_rows(rows[2], g4)
-                cat[:, c1 + c2:] = D2.rows_of(self.pool4x(D2.maps_of(f4, g4.maps, g4.height, g4.width)))
+                self._join(self.self_fusion_4x.run_act(rows[2], g4), g4, cat[:, c1 + c2:], pool=True)
             with torch.cuda.stream(s1):
-                f1 = self.self_fusion_1x.run_rows(rows[0], g1)
-                up = upsample2x_bilinear(D2.maps_of(f1, g1.maps, g1.height, g1.width))
-                cat[:, 0:c1] = D2.rows_of(up)
+                self._join(self.self_fusion_1x.run_act(rows[0], g1), g1, cat[:, 0:c1], pool=False)
             self.self_fusion_2x.run_rows(rows[1], g2, out=cat[:, c1:c1 + c2])
             main.wait_stream(s1)
             main.wait_stream(s4)
@@ -125,6 +123,17 @@ class Occupancy_Initialization(nn.Module):
             for blk in (self.post_fusion_1, self.post_fusion_2, self.post_fusion_3, self.post_fusion_4):
                 a = blk.run_act(a, g2)
             return D2.maps_of(D2.materialize(a), g2.maps, g2.height, g2.width)
+
+    def _join(self, act, grid, dst, pool):
+        """an outer level onto the 1/8 grid and into its slice `dst` of the concat buffer: 2x2 mean (pool) or bilinear x2.
+        One launch from the level's raw rows and pending BatchNorm; EPRECON_INIT_GLUE=0 (or a BatchNorm held as accumulators):
+        materialise, resample, copy into the slice"""
+        # (x2 with C % 4 != 0: upsample2x_bilinear leaves such maps to the framework, whose arithmetic the kernel does not restate)
+        if act.scale is not None and (pool or act.rows.shape[1] % 4 == 0) and _lib.load().eprecon_init_glue():
+            return (D2.affine_pool2_rows if pool else D2.affine_up2_rows)(act, grid, dst)
+        maps = D2.maps_of(D2.materialize(act), grid.maps, grid.height, grid.width)
+        dst[:] = D2.rows_of(self.pool4x(maps) if pool else upsample2x_bilinear(maps))
+        return dst
 
     def _fusion_graphed(self, views):
         """feat_fusion_pre through a captured HIP graph (inference only; the result buffer is reused
@@ -136,7 +145,7 @@ class Occupancy_Initialization(nn.Module):
         # inside it used to (HIP convolution path, float32 contiguous maps, <= 16 views; otherwise stacked NCHW inputs as before).
         direct = self.use_hip_conv and len(views[0]) <= 16 and all(
             m.dtype == torch.float32 and m.is_contiguous() for v in views for m in v)
-        key = key + (direct,)
+        key = key + (direct, bool(_lib.load().eprecon_init_glue()))     # (the joins of the capture follow the switch)
         entry = self._graphs.get(key)
         if entry is None:
             shapes = [(len(v),) + tuple(v[0].shape) for v in views]
@@ -198,7 +207,20 @@ class Occupancy_Initialization(nn.Module):
         the count and starts issuing the submanifold stack (inference on the GPU only; ignored otherwise)."""
         bs = features_all[0][0].shape[0]
         dev = features_all[0][0].device
-        graphed = self.use_hip_graph and not torch.is_grad_enabled() and dev.type == "cuda"
+        self.dense_map = None    # one batch element on the dense-grid path: the set's sparse.DenseMap, for the stage-0 selection
+        on_gpu = dev.type == "cuda" and not torch.is_grad_enabled()
+        graphed = self.use_hip_graph and on_gpu
+        glue = on_gpu and bool(_lib.load().eprecon_init_glue())     # (EPRECON_INIT_GLUE=0: the launches as they were)
+        interval = 2 ** (2 - stage)
+        # a dense raster of `shape` (tagged by its maker): the gather writes the rank volume the dense-grid layers want
+        rank = BP.dense_rank_buffer(coords, shape, interval) if glue and bs == 1 else None
+        counted = None
+        if glue and bs == 1 and self.use_hip_conv:
+            # the count half of the variance call reads coordinates and matrices only: it runs beside the 2D stack, whose
+            # result (channels-last [V,1,d,H/8,W/8] on this path) only the gather half waits for
+            h8, w8 = features_all[0][1].shape[-2:]
+            counted = BP.count_async(coords, origin, voxel_size, (len(features_all), 1, self.ch_down, h8, w8), KRcam,
+                                     min_view_number, BP.MODE_VARIANCE, stream=_lib.side_stream(dev, _lib.SIDE_SETUP))
         per_batch = []
         for b in range(bs):
             # per-view maps of batch element b: 1/16 [80,h,w], 1/8 [40,2h,2w], 1/4 [24,4h,4w]
@@ -209,10 +231,12 @@ class Occupancy_Initialization(nn.Module):
             else:
                 per_batch.append(self.feat_fusion_pre(*[torch.stack(v) for v in views]))
         fused = per_batch[0].unsqueeze(1) if bs == 1 else torch.stack(per_batch, dim=1)  # [V,B,32,H,W]
-        if between is not None and dev.type == "cuda" and not torch.is_grad_enabled():
+        if on_gpu and (between is not None or glue):
+            # (the view mean is stored for the backward pass only: not here, unless EPRECON_INIT_GLUE=0 asks for the old launches)
             pend = BP.run_async(coords, origin, voxel_size, fused, KRcam, min_view_number, BP.MODE_VARIANCE,
-                                min_valid_per_batch=INIT_MIN_VALID, want_mean=True)
-            between()
+                                min_valid_per_batch=INIT_MIN_VALID, want_mean=not glue, rank_out=rank, counted=counted)
+            if between is not None:
+                between()
             res = pend.result()
             if res is not None:
                 res["var"] = res.pop("feats")
@@ -221,7 +245,6 @@ class Occupancy_Initialization(nn.Module):
                                    min_valid=INIT_MIN_VALID)
         if res is None:
             return None
-        interval = 2 ** (2 - stage)
         coord_valid = res["coords"]
         parts = []
         start = 0
@@ -231,9 +254,11 @@ class Occupancy_Initialization(nn.Module):
             seg = slice(start, start + nb)
             # the valid voxels are a raster-ordered subset of the dense `shape` grid (generate_grid): well filled, so the
             # 3x3x3 layers of the stack take the dense-grid kernel (no hash grid, no kernel map)
-            vset = SP.VoxelSet(coord_valid[seg], interval, dims=shape)
+            vset = SP.VoxelSet(coord_valid[seg], interval, dims=shape, rank=rank)
             parts.append(self.sparse_stack(res["var"][seg], vset))
             start += nb
+            if bs == 1:
+                self.dense_map = vset._dense
         occ = parts[0] if bs == 1 else torch.cat(parts)
         out_coords = coord_valid if coords.dtype == torch.int32 else coord_valid.to(coords.dtype)
         return [occ, out_coords, res["count"]]

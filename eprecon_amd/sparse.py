@@ -142,10 +142,16 @@ class DenseMap:
     int32[gx*gy*gz (+1)] (cell -> row or -1, eprecon_grid_rank_async) instead of a hash grid + [27, N] kernel map.
     Layers whose shape the tile kernel does not take fall back to the set's kernel map (built on first use)."""
 
-    def __init__(self, vset, dims):
+    def __init__(self, vset, dims, rank=None):
+        """rank: the volume when its producer wrote it already (the back-projection of a dense raster,
+        back_project.dense_rank_buffer: every row on the grid by construction) — nothing is launched and nothing checked"""
         lib = _lib.load()
         self.vset, self.dims = vset, tuple(int(d) for d in dims)
         gx, gy, gz = self.dims
+        if rank is not None:
+            assert rank.dtype == torch.int32 and rank.numel() == gx * gy * gz + 1 and rank.device == vset.coords.device
+            self.rank = rank
+            return
         self.rank = torch.empty(gx * gy * gz + 1, dtype=torch.int32, device=vset.coords.device)
         _lib.check(lib.eprecon_grid_rank_async(_lib.ptr(vset.coords), vset.n, vset.stride, gx, gy, gz, _lib.ptr(self.rank),
                                                _lib.current_stream()), "eprecon_grid_rank_async")
@@ -394,9 +400,10 @@ class VoxelSet:
     """A set of active voxels at one tensor stride: coords int32[N,4] (b,x,y,z), its hash grid and
     the kernel maps built on it.  Maps are built once and reused by every layer on the set.
     `dims` (optional): the set lives on the dense grid of dims cells of `stride` voxels starting at 0 (a raster of
-    generate_grid, ops/generate_grids.py:3-10) — its 3x3x3 layers then run on the dense-grid kernel when it is full enough."""
+    generate_grid, ops/generate_grids.py:3-10) — its 3x3x3 layers then run on the dense-grid kernel when it is full enough.
+    `rank` (optional, with dims): the grid's rank volume int32[cells + 1], already written by the set's producer."""
 
-    def __init__(self, coords, stride=1, grid=None, dims=None):
+    def __init__(self, coords, stride=1, grid=None, dims=None, rank=None):
         assert coords.dtype == torch.int32 and coords.dim() == 2 and coords.shape[1] == 4
         self.coords = coords.contiguous()
         self.stride = int(stride)
@@ -405,6 +412,7 @@ class VoxelSet:
         self._k3 = None
         self._down = None
         self._dense = None
+        self._rank = rank        # the rank volume of `dims` when the set's producer wrote it (DenseMap)
 
     def conv_map(self, ksize=3):
         """what a stride-1 k=3 layer on this set takes as its map: a DenseMap for a well-filled dense grid, else the
@@ -413,7 +421,7 @@ class VoxelSet:
         if self.dims is not None and self.n >= DENSE_MIN_FILL * self.dims[0] * self.dims[1] * self.dims[2] \
                 and _dense3d_level() > 0 and self.coords.is_cuda:
             if self._dense is None:
-                self._dense = DenseMap(self, self.dims)
+                self._dense = DenseMap(self, self.dims, rank=self._rank)
             return self._dense
         return self.kernel_map(3)
 

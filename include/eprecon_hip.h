@@ -98,6 +98,39 @@ int eprecon_back_project(const int32_t *coords, int64_t n, const float *origin, 
                          void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * eprecon_back_project_async in two halves, for channels-last maps (EPRECON_LAYOUT_NHWC) only.  EPRECON_BP_COUNT queues what
+ * depends on the coordinates and matrices alone (count[], the tile totals in `workspace`; feats may be NULL); EPRECON_BP_GATHER
+ * queues the rest.  Both take the same arguments and the same workspace, whose contents must survive in between; the count
+ * half may run on another stream as long as it has finished when the gather half starts.  Count then gather on one stream
+ * is the one-call form, launch for launch.
+ */
+#define EPRECON_BP_COUNT 1
+#define EPRECON_BP_GATHER 2
+int eprecon_back_project_phase_async(int phase, const int32_t *coords, int64_t n, const float *origin, int batch,
+                                     float voxel_size, const float *feats, int feats_layout,
+                                     const float *krcam, int n_views, int channels, int height,
+                                     int width, int min_view, int mode, float *out_feats,
+                                     float *out_mean, int32_t *out_coords, float *count,
+                                     float *out_grid, uint8_t *out_mask, int32_t *n_valid_dev,
+                                     void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * For a list that IS the x-major raster of a dense grid (entry e = cell e, one batch element): the NEXT
+ * eprecon_back_project_async / eprecon_back_project call of the calling host thread (or gather half) also writes rank int32[n + 1] —
+ * rank[e] = output row of entry e or -1, rank[n] = 0 — which is the rank volume eprecon_grid_rank_async would build from
+ * the call's out_coords (its trailing word counts voxels off the grid: none here).  One-shot: that call takes the pointer
+ * whatever it returns.  NULL disarms.
+ */
+int eprecon_back_project_rank_out(int32_t *rank);
+
+/*
+ * EPRECON_INIT_GLUE (read at every call): 1 unless the variable is set to 0.  0 keeps the occupancy-initialisation branch on
+ * its separate glue launches: rank volume by eprecon_grid_rank_async, finalize + apply for BatchNorms of <= 4 channels, the
+ * list form of the stage-0 selection ("Switches").  The host wrappers ask here, so that one reading decides.
+ */
+int eprecon_init_glue(void);
+
+/*
  * Per-kernel timing hook (what bench.py's roofline line is measured with).  While enabled, every
  * eprecon_back_project*_ call brackets its gather kernel with two hipEvents recorded on the
  * caller's stream.  eprecon_profile_gather_ms() synchronises on the last stop event and returns
@@ -349,6 +382,18 @@ int eprecon_batchnorm_finalize_affine_async(const float *partial, int64_t nblk, 
 /* out[i, c] = [relu]( x[i, c] * scale[c] + shift[c] ); out may alias x */
 int eprecon_affine_rows_async(const float *x, int64_t n, int channels, int ld_x, const float *scale,
                               const float *shift, int relu, float *out, int ld_out, void *stream);
+/*
+ * The joins of the 2D fusion stack in one launch each.  x: the pixel rows f32[maps*height*width, channels] (row stride ld_x)
+ * of a level with its pending BatchNorm (scale, shift, relu), applied on load as eprecon_affine_rows_async does.
+ *   pool2  out row (m, y, x) of the (height/2) x (width/2) grid = mean of the 2x2 block at (2y, 2x): sum in (kh, kw) order,
+ *          then the divide (the arithmetic of a channels-last average pooling, kernel 2, stride 2)
+ *   up2    out row (m, y, x) of the 2 height x 2 width grid = the bilinear x2 sample of eprecon_upsample2x_nhwc_async
+ * out has row stride ld_out >= channels (a channel slice of a concat buffer).  No allocation: capture-safe.
+ */
+int eprecon_affine_pool2_rows_async(const float *x, int maps, int height, int width, int channels, int ld_x, const float *scale,
+                                    const float *shift, int relu, float *out, int ld_out, void *stream);
+int eprecon_affine_up2_rows_async(const float *x, int maps, int height, int width, int channels, int ld_x, const float *scale,
+                                  const float *shift, int relu, float *out, int ld_out, void *stream);
 /* out[i, c] = [relu]( x[i, c] * scale[c] + shift[c] + residual[i, c] ): the tail of the residual blocks
  * (models/modules.py:46-72) from a producer-finished BatchNorm; residual may be NULL; out may alias x */
 int eprecon_affine_rows_res_async(const float *x, int64_t n, int channels, int ld_x, const float *scale,
@@ -440,6 +485,16 @@ size_t eprecon_init_select_workspace_bytes(int batch, int dim);
 int eprecon_init_select_async(const float *logit, const int32_t *coords, int64_t n, float threshold,
                               int batch, int dim, int cell, int32_t *out_coords, int32_t *n_out_dev,
                               void *workspace, size_t workspace_bytes, void *stream);
+/*
+ * The same for ONE batch element whose voxels are rows of a dense grid_x x grid_y x grid_z grid of `stride` voxels
+ * (cell % stride == 0) whose rank volume the caller holds (rank int32[grid_x*grid_y*grid_z]: cell -> row or -1,
+ * eprecon_grid_rank_async): the marks are written in full by one launch over the coarse cells, without a clear and
+ * without a pass over the list.  Same coordinates, counts and order.  EPRECON_INIT_GLUE=0 runs the list form.
+ */
+int eprecon_init_select_dense_async(const float *logit, const int32_t *coords, int64_t n, const int32_t *rank, int grid_x,
+                                    int grid_y, int grid_z, int stride, float threshold, int dim, int cell,
+                                    int32_t *out_coords, int32_t *n_out_dev, void *workspace, size_t workspace_bytes,
+                                    void *stream);
 /*
  * Sparsify for the next stage (models/neucon_network.py:454-507) in one call: occupancy = occ > threshold; the kept rows of
  * coords / tsdf / occ / feat_all compacted in row order (torch.nonzero + index_select + cat of the reference) and the counts
