@@ -2,7 +2,7 @@
 
 The reference trains through torchsparse's / spconv's own autograd (main.py:181-313: loss.backward() through
 spnn.Conv3d, SubMConv3d, spvoxelize, spdevoxelize and F.grid_sample).  Here every forward is the same HIP entry point
-the inference path calls, and every backward is a HIP kernel as well (csrc/backward.hip, csrc/back_project.hip):
+the inference path calls, and every backward is a HIP kernel as well (csrc/backward.hip, csrc/back_project_backward.hip):
 
   sparse_conv        dx: the forward gather-GEMM on the inverted kernel map with transposed weights;
                      dW: eprecon_sparse_conv_wgrad_async (fp32 MFMA over compacted rows, deterministic); db: column sums
@@ -197,8 +197,7 @@ class _BackProjectGrad(torch.autograd.Function):
         dout = dout.contiguous()
         dmean = dmean.contiguous() if (dmean is not None and ctx.has_mean) else None
         dfeats = torch.empty((v, b, h, w, c), dtype=torch.float32, device=dev)
-        origin_f = origin.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
-        krcam_f = krcam.to(device=dev, dtype=torch.float32).contiguous()
+        coords_valid, origin_f, krcam_f = BP._prep_inputs(coords_valid, origin, krcam, v, b, dev)
         # (the deterministic form: 64-bit fixed-point accumulation with integer atomics, converted at the end)
         ws = _lib.workspace(lib.eprecon_back_project_backward_workspace_bytes(b, v, c, h, w), dev)
         _lib.check(lib.eprecon_back_project_backward_det_async(

@@ -18,6 +18,8 @@ from . import _lib
 
 MODE_MEAN, MODE_MEAN_DEPTH, MODE_VARIANCE = 0, 1, 2
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
+
+
 def mark_dense(coords, dims, interval, batch=1):
     """Tag `coords` (int32[B*Dx*Dy*Dz, 4]) as the dense x-major raster of a dims grid at spacing `interval` — what
     generate_grids.dense_coords / ops/generate_grids.py:3-10 produce.  A plain attribute (lost by any op that makes a new
@@ -58,6 +60,52 @@ def _prep_feats(feats):
     return feats.contiguous(), LAYOUT_NCHW
 
 
+def _prep_inputs(coords, origin, krcam, v, b, dev):
+    """-> (coords int32[N, 4], origin f32[B, 3], krcam f32[V, B, 4, 4]), contiguous and on `dev`, for V views of B batch elements"""
+    if dev.type != "cuda":
+        raise _lib.EpreconError("eprecon_amd operators need device tensors (no CPU fallback)")
+    coords_i = (coords if coords.dtype == torch.int32 else coords.to(torch.int32)).contiguous()
+    origin_f = origin.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+    krcam_f = krcam.to(device=dev, dtype=torch.float32).contiguous()
+    assert krcam_f.shape == (v, b, 4, 4) and origin_f.shape[0] == b
+    return coords_i, origin_f, krcam_f
+
+
+def _alloc_outputs(n, v, c, mode, want_grid, want_mean, dev, count=None):
+    """the output tensors of one call, sized for n valid rows (count: the count half's, when there was one)"""
+    f32 = dict(dtype=torch.float32, device=dev)
+    return {"feats": torch.empty((n, c + 1 if mode == MODE_MEAN_DEPTH else c), **f32),
+            "coords": torch.empty((n, 4), dtype=torch.int32, device=dev),
+            "count": torch.empty((n,), **f32) if count is None else count,
+            "mean": torch.empty((n, c), **f32) if want_mean else None,
+            "grid": torch.empty((v * n * 2,), **f32) if want_grid else None,
+            "mask": torch.empty((v * n,), dtype=torch.uint8, device=dev) if want_grid else None}
+
+
+def _lib_args(inputs, voxel_size, feats, layout, shape, min_view, mode, t, n_valid_dev, ws, extra=()):
+    """the argument tuple of eprecon_back_project_async (phase_async: behind the phase); t: _alloc_outputs(...) or, for the count
+    half, {"count": ...}; extra: what eprecon_back_project takes between `mode` and the outputs, and behind `n_valid_dev`"""
+    coords_i, origin_f, krcam_f = inputs
+    v, b, c, h, w = shape
+    p = lambda k: _lib.ptr(t.get(k))
+    return (_lib.ptr(coords_i), coords_i.shape[0], _lib.ptr(origin_f), b, float(voxel_size), _lib.ptr(feats), layout, _lib.ptr(krcam_f),
+            v, c, h, w, int(min_view), mode, *extra[:1], p("feats"), p("mean"), p("coords"), p("count"), p("grid"), p("mask"),
+            _lib.ptr(n_valid_dev), *extra[1:], _lib.ptr(ws), ws.numel(), _lib.current_stream())
+
+
+def _result(t, v, n_valid, per_batch, want_grid, want_mean, sliced=True):
+    """what run() returns, from the tensors of _alloc_outputs; sliced=False: every row is valid (n_valid == N)"""
+    cut = (lambda x, k=1: x[:k * n_valid]) if sliced else (lambda x, k=1: x)
+    res = {"feats": cut(t["feats"]), "coords": cut(t["coords"]), "count": t["count"], "n_valid": n_valid,
+           "n_valid_per_batch": per_batch}
+    if want_grid:
+        res["grid"] = cut(t["grid"], v * 2).view(v, n_valid, 2)
+        res["mask"] = cut(t["mask"], v).view(v, n_valid).bool()
+    if want_mean:
+        res["mean"] = cut(t["mean"])
+    return res
+
+
 class PendingBackProject:
     """A back-projection whose kernels are queued on a stream; `result()` waits for the valid counts
     (pinned host copy + event) and returns what `run()` returns.  Lets independent levels be issued
@@ -75,15 +123,7 @@ class PendingBackProject:
         """counts: the 1 + B values of `n_valid_dev` as read by the caller (hold_read: together with other counts)"""
         if any(x < self._min_valid for x in counts[1:]):
             return None  # reference: `return None`
-        nv, t, v = counts[0], self._t, self._v
-        res = {"feats": t["feats"][:nv], "coords": t["coords"][:nv], "count": t["count"], "n_valid": nv,
-               "n_valid_per_batch": counts[1:]}
-        if self._want_grid:
-            res["grid"] = t["grid"][: v * nv * 2].view(v, nv, 2)
-            res["mask"] = t["mask"][: v * nv].view(v, nv).bool()
-        if self._want_mean:
-            res["mean"] = t["mean"][:nv]
-        return res
+        return _result(self._t, self._v, counts[0], counts[1:], self._want_grid, self._want_mean)
 
 
 class CountedBackProject:
@@ -100,14 +140,9 @@ def count_async(coords, origin, voxel_size, feats_shape, krcam, min_view, mode=M
     Same launches as the one-call form (eprecon_back_project_phase_async)."""
     lib = _lib.load()
     dev = coords.device
-    if dev.type != "cuda":
-        raise _lib.EpreconError("eprecon_amd operators need device tensors (no CPU fallback)")
-    v, b, c, h, w = (int(x) for x in feats_shape)
+    shape = v, b, c, h, w = tuple(int(x) for x in feats_shape)
+    inputs = _prep_inputs(coords, origin, krcam, v, b, dev)
     n = coords.shape[0]
-    coords_i = (coords if coords.dtype == torch.int32 else coords.to(torch.int32)).contiguous()
-    origin_f = origin.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
-    krcam_f = krcam.to(device=dev, dtype=torch.float32).contiguous()
-    assert krcam_f.shape == (v, b, 4, 4) and origin_f.shape[0] == b
     count = torch.empty((n,), dtype=torch.float32, device=dev)
     n_valid_dev = torch.empty((1 + b,), dtype=torch.int32, device=dev)
     # a buffer of the call's own, not the stream's grow-only scratch: it has to survive until the gather half has run
@@ -115,17 +150,15 @@ def count_async(coords, origin, voxel_size, feats_shape, krcam, min_view, mode=M
 
     def queue():
         _lib.check(lib.eprecon_back_project_phase_async(
-            1, _lib.ptr(coords_i), n, _lib.ptr(origin_f), b, float(voxel_size), None, LAYOUT_NHWC, _lib.ptr(krcam_f), v, c, h, w,
-            int(min_view), mode, None, None, None, _lib.ptr(count), None, None, _lib.ptr(n_valid_dev), _lib.ptr(ws), ws.numel(),
-            _lib.current_stream()), "eprecon_back_project_phase_async")
+            1, *_lib_args(inputs, voxel_size, None, LAYOUT_NHWC, shape, min_view, mode, {"count": count}, n_valid_dev, ws)),
+            "eprecon_back_project_phase_async")
     if stream is None:
         queue()
     else:
         stream.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(stream):
             queue()
-    return CountedBackProject((v, b, c, h, w), (coords_i, origin_f, krcam_f, float(voxel_size), int(min_view), mode), count,
-                              n_valid_dev, ws, stream)
+    return CountedBackProject(shape, inputs + (float(voxel_size), int(min_view), mode), count, n_valid_dev, ws, stream)
 
 
 def run_async(coords, origin, voxel_size, feats, krcam, min_view, mode=MODE_MEAN, min_valid_per_batch=1,
@@ -138,48 +171,29 @@ def run_async(coords, origin, voxel_size, feats, krcam, min_view, mode=MODE_MEAN
     counted: count_async(...)'s result for these very arguments — only the gather half is queued here."""
     lib = _lib.load()
     dev = feats.device
-    if dev.type != "cuda":
-        raise _lib.EpreconError("eprecon_amd operators need device tensors (no CPU fallback)")
-    v, b, c, h, w = feats.shape
+    shape = v, b, c, h, w = tuple(feats.shape)
+    inputs = _prep_inputs(coords, origin, krcam, v, b, dev)
     n = coords.shape[0]
-    coords_i = coords if coords.dtype == torch.int32 else coords.to(torch.int32)
-    coords_i = coords_i.contiguous()
-    origin_f = origin.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
-    krcam_f = krcam.to(device=dev, dtype=torch.float32).contiguous()
-    assert krcam_f.shape == (v, b, 4, 4) and origin_f.shape[0] == b
     feats_c, layout = _prep_feats(feats)
-    cout = c + 1 if mode == MODE_MEAN_DEPTH else c
+    t = _alloc_outputs(n, v, c, mode, want_grid, want_mean, dev, count=None if counted is None else counted.count)
     if counted is not None:
-        assert layout == LAYOUT_NHWC and counted.shape == (v, b, c, h, w) and not extra_words
+        assert layout == LAYOUT_NHWC and counted.shape == shape and not extra_words
         assert counted.inputs[3:] == (float(voxel_size), int(min_view), mode) and counted.count.shape[0] == n
-        coords_i, origin_f, krcam_f = counted.inputs[:3]
-
-    t = {"feats": torch.empty((n, cout), dtype=torch.float32, device=dev),
-         "coords": torch.empty((n, 4), dtype=torch.int32, device=dev),
-         "count": torch.empty((n,), dtype=torch.float32, device=dev) if counted is None else counted.count,
-         "mean": torch.empty((n, c), dtype=torch.float32, device=dev) if want_mean else None,
-         "grid": torch.empty((v * n * 2,), dtype=torch.float32, device=dev) if want_grid else None,
-         "mask": torch.empty((v * n,), dtype=torch.uint8, device=dev) if want_grid else None}
-    if counted is not None:
-        n_valid_dev, ws = counted.n_valid_dev, counted.ws
+        inputs, n_valid_dev, ws = counted.inputs[:3], counted.n_valid_dev, counted.ws
         if counted.stream is not None:
             torch.cuda.current_stream(dev).wait_stream(counted.stream)
     else:
         n_valid_dev = torch.empty((1 + b + int(extra_words),), dtype=torch.int32, device=dev)
-        ws_bytes = lib.eprecon_back_project_workspace_bytes(n, b, v, c, h, w, layout)
-        ws = _lib.workspace(ws_bytes, dev)
+        ws = _lib.workspace(lib.eprecon_back_project_workspace_bytes(n, b, v, c, h, w, layout), dev)
     _arm_rank(lib, rank_out, n, b)
-    tail = (_lib.ptr(coords_i), n, _lib.ptr(origin_f), b, float(voxel_size), _lib.ptr(feats_c), layout,
-            _lib.ptr(krcam_f), v, c, h, w, int(min_view), mode, _lib.ptr(t["feats"]), _lib.ptr(t["mean"]),
-            _lib.ptr(t["coords"]), _lib.ptr(t["count"]), _lib.ptr(t["grid"]), _lib.ptr(t["mask"]),
-            _lib.ptr(n_valid_dev), _lib.ptr(ws), ws.numel(), _lib.current_stream())
+    args = _lib_args(inputs, voxel_size, feats_c, layout, shape, min_view, mode, t, n_valid_dev, ws)
     if counted is not None:
-        _lib.check(lib.eprecon_back_project_phase_async(2, *tail), "eprecon_back_project_phase_async")
+        _lib.check(lib.eprecon_back_project_phase_async(2, *args), "eprecon_back_project_phase_async")
     else:
-        _lib.check(lib.eprecon_back_project_async(*tail), "eprecon_back_project_async")
+        _lib.check(lib.eprecon_back_project_async(*args), "eprecon_back_project_async")
     read = None if hold_read else _lib.PinnedRead(n_valid_dev[:1 + b])
     # inputs stay referenced until result(): the kernels may still be reading them
-    t["_keep"] = (coords_i, origin_f, krcam_f, feats_c, n_valid_dev, ws if counted is not None else None)
+    t["_keep"] = (*inputs, feats_c, n_valid_dev, ws if counted is not None else None)
     pend = PendingBackProject(t, n, v, c, b, int(min_valid_per_batch), read, want_grid, want_mean)
     pend.n_valid_dev, pend.coords_all = n_valid_dev, t["coords"]
     return pend
@@ -191,28 +205,13 @@ def run(coords, origin, voxel_size, feats, krcam, min_view, mode=MODE_MEAN, min_
     {feats [n_valid, C(+1)], coords int32 [n_valid, 4], count f32 [N], n_valid, (grid, mask, mean)}."""
     lib = _lib.load()
     dev = feats.device
-    if dev.type != "cuda":
-        raise _lib.EpreconError("eprecon_amd operators need device tensors (no CPU fallback)")
-    v, b, c, h, w = feats.shape
+    shape = v, b, c, h, w = tuple(feats.shape)
+    inputs = _prep_inputs(coords, origin, krcam, v, b, dev)
     n = coords.shape[0]
-    coords_i = coords if coords.dtype == torch.int32 else coords.to(torch.int32)
-    coords_i = coords_i.contiguous()
-    origin_f = origin.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
-    krcam_f = krcam.to(device=dev, dtype=torch.float32).contiguous()
-    assert krcam_f.shape == (v, b, 4, 4) and origin_f.shape[0] == b
     feats_c, layout = _prep_feats(feats)
-    cout = c + 1 if mode == MODE_MEAN_DEPTH else c
-
-    out_feats = torch.empty((n, cout), dtype=torch.float32, device=dev)
-    out_coords = torch.empty((n, 4), dtype=torch.int32, device=dev)
-    count = torch.empty((n,), dtype=torch.float32, device=dev)
-    out_mean = torch.empty((n, c), dtype=torch.float32, device=dev) if want_mean else None
-    out_grid = torch.empty((v * n * 2,), dtype=torch.float32, device=dev) if want_grid else None
-    out_mask = torch.empty((v * n,), dtype=torch.uint8, device=dev) if want_grid else None
+    t = _alloc_outputs(n, v, c, mode, want_grid, want_mean, dev)
     n_valid_dev = torch.empty((1 + b,), dtype=torch.int32, device=dev)
-    n_valid_host = (ctypes.c_int32 * (1 + b))()
-    ws_bytes = lib.eprecon_back_project_workspace_bytes(n, b, v, c, h, w, layout)
-    ws = _lib.workspace(ws_bytes, dev)
+    ws = _lib.workspace(lib.eprecon_back_project_workspace_bytes(n, b, v, c, h, w, layout), dev)
 
     if min_view <= 0 and b == 1 and n >= max(int(min_valid_per_batch), 1):
         # every voxel is valid (the view count is never negative; the one batch element owns all rows): nothing to wait for.
@@ -220,38 +219,18 @@ def run(coords, origin, voxel_size, feats, krcam, min_view, mode=MODE_MEAN, min_
         # range is the one way a row can drop out).
         _arm_rank(lib, rank_out, n, b)
         _lib.check(lib.eprecon_back_project_async(
-            _lib.ptr(coords_i), n, _lib.ptr(origin_f), b, float(voxel_size), _lib.ptr(feats_c), layout,
-            _lib.ptr(krcam_f), v, c, h, w, int(min_view), mode, _lib.ptr(out_feats), _lib.ptr(out_mean), _lib.ptr(out_coords),
-            _lib.ptr(count), _lib.ptr(out_grid), _lib.ptr(out_mask), _lib.ptr(n_valid_dev), _lib.ptr(ws), ws.numel(),
-            _lib.current_stream()), "eprecon_back_project_async")
+            *_lib_args(inputs, voxel_size, feats_c, layout, shape, min_view, mode, t, n_valid_dev, ws)), "eprecon_back_project_async")
         _lib.defer_check(n_valid_dev[0:1], n, "back-projection with min_view <= 0: rows with a batch index out of range")
-        res = {"feats": out_feats, "coords": out_coords, "count": count, "n_valid": n, "n_valid_per_batch": [n]}
-        if want_grid:
-            res["grid"] = out_grid.view(v, n, 2)
-            res["mask"] = out_mask.view(v, n).bool()
-        if want_mean:
-            res["mean"] = out_mean
-        return res
+        return _result(t, v, n, [n], want_grid, want_mean, sliced=False)
+    n_valid_host = (ctypes.c_int32 * (1 + b))()
     _lib.count_host_read()
     _arm_rank(lib, rank_out, n, b)
-    rc = lib.eprecon_back_project(
-        _lib.ptr(coords_i), n, _lib.ptr(origin_f), b, float(voxel_size), _lib.ptr(feats_c), layout,
-        _lib.ptr(krcam_f), v, c, h, w, int(min_view), mode, int(min_valid_per_batch),
-        _lib.ptr(out_feats), _lib.ptr(out_mean), _lib.ptr(out_coords), _lib.ptr(count),
-        _lib.ptr(out_grid), _lib.ptr(out_mask), _lib.ptr(n_valid_dev),
-        ctypes.cast(n_valid_host, ctypes.c_void_p), _lib.ptr(ws), ws.numel(), _lib.current_stream())
+    rc = lib.eprecon_back_project(*_lib_args(inputs, voxel_size, feats_c, layout, shape, min_view, mode, t, n_valid_dev, ws,
+                                             extra=(int(min_valid_per_batch), ctypes.cast(n_valid_host, ctypes.c_void_p))))
     _lib.drain_deferred()          # (the library copied the counts itself: pending checks are verified here, when there are any)
     if not _lib.check(rc, "eprecon_back_project"):
         return None
-    nv = int(n_valid_host[0])
-    res = {"feats": out_feats[:nv], "coords": out_coords[:nv], "count": count, "n_valid": nv,
-           "n_valid_per_batch": [int(x) for x in n_valid_host[1:]]}
-    if want_grid:
-        res["grid"] = out_grid[: v * nv * 2].view(v, nv, 2)
-        res["mask"] = out_mask[: v * nv].view(v, nv).bool()
-    if want_mean:
-        res["mean"] = out_mean[:nv]
-    return res
+    return _result(t, v, int(n_valid_host[0]), [int(x) for x in n_valid_host[1:]], want_grid, want_mean)
 
 
 def back_project(coords, origin, voxel_size, feats, KRcam, min_view_number):
@@ -262,6 +241,12 @@ def back_project(coords, origin, voxel_size, feats, KRcam, min_view_number):
         return None
     # the reference concatenates onto torch.empty(0, 4) (float32), so its coords come back as float
     return [res["feats"], res["coords"].to(torch.float32), res["count"]]
+
+
+def _forward_list(res, coords):
+    """Back_Project.forward's return value from run()'s dict: the coordinates come back in the dtype they came in"""
+    out_coords = res["coords"] if coords.dtype == torch.int32 else res["coords"].to(coords.dtype)
+    return [res["feats"], out_coords, res.get("grid"), res.get("mask"), res["count"]]
 
 
 class Back_Project(nn.Module):
@@ -283,10 +268,7 @@ class Back_Project(nn.Module):
         else:
             res = run(coords, origin, voxel_size, feats, KRcam, min_view_number, MODE_MEAN,
                       want_grid=self.return_projection)
-        if res is None:
-            return None
-        out_coords = res["coords"] if coords.dtype == torch.int32 else res["coords"].to(coords.dtype)
-        return [res["feats"], out_coords, res.get("grid"), res.get("mask"), res["count"]]
+        return None if res is None else _forward_list(res, coords)
 
 
 def get_img_feats(coords, origin, voxel_size, feats, KRcam, min_view_number):
@@ -311,8 +293,7 @@ def forward_behind(module, coords, origin, voxel_size, feats, KRcam, min_view_nu
     res = pend.result_from(host[:nb])
     if res is None:
         return None, None
-    out_coords = res["coords"] if coords.dtype == torch.int32 else res["coords"].to(coords.dtype)
-    return [res["feats"], out_coords, res.get("grid"), res.get("mask"), res["count"]], finish(res["n_valid"], host[nb:])
+    return _forward_list(res, coords), finish(res["n_valid"], host[nb:])
 
 
 def view_variance(coords, origin, voxel_size, feats_fused, KRcam, min_view_number, min_valid=1000, rank_out=None):

@@ -9,6 +9,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "../../include/eprecon_hip.h"
 
 #define EP_HIP_CHECK(expr)                                            \
@@ -31,6 +33,29 @@ inline bool switch_off(const char *name)
 {
     const char *e = getenv(name);
     return e && e[0] == '0';
+}
+
+// A run-time value picks a template argument: f (a generic lambda) gets, as a std::integral_constant, the X of the list that
+// equals x; the last X of the list takes every other value.
+template <int X, int... Rest, class F>
+int pick(int x, F &&f)
+{
+    if constexpr (sizeof...(Rest) == 0) return f(std::integral_constant<int, X>{});
+    else return x == X ? f(std::integral_constant<int, X>{}) : pick<Rest...>(x, f);
+}
+
+// Dynamic LDS a workgroup may ask for when its kernel has not opted in to more (hipFuncAttributeMaxDynamicSharedMemorySize; the
+// back-projection kernels do not): what the device reports per workgroup (a property query), and never more than 64 KiB.
+static inline size_t dynamic_lds_limit()
+{
+    static const size_t limit = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || v <= 0)
+            v = 64 * 1024;
+        return (size_t)(v < 64 * 1024 ? v : 64 * 1024);
+    }();
+    return limit;
 }
 
 // Hardware block id -> logical block id.  The dispatcher places hardware block h on XCD h % 8
@@ -113,7 +138,7 @@ struct Fork {
 };
 int fork_for(hipStream_t main, Fork &out);
 
-// the gather-kernel timing hook of eprecon_profile_enable (back_project.hip), for the other gather variants
+// the gather-kernel timing hook of eprecon_profile_enable (profile.hip): every gather variant brackets its launch with these
 int profile_bracket_begin(hipStream_t st);
 int profile_bracket_end(hipStream_t st, const char *kernel);
 

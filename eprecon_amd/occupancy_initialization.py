@@ -2,7 +2,7 @@
 
 Per batch element: fuse the three pyramid levels of the 9 views into 32-channel 1/8-resolution maps
 (dense 2D convolutions, PyTorch-ROCm), back-project them onto the dense 48^3 grid and take the
-per-voxel variance over the visible views (HIP, csrc/back_project.hip), then run the submanifold
+per-voxel variance over the visible views (HIP, csrc/back_project.hip; backward: csrc/back_project_backward.hip), then run the submanifold
 stack BN -> sparse ELAN -> 3 x (SubM3 + ReLU + residual + LN) -> SubM3(32->1) -> BN on the voxels
 seen by >= min_view views (HIP: hash-grid kernel map built once, MFMA gather-GEMM convolutions,
 fused normalisation epilogues).  Returns [occupancy logit f32[N_valid,1], coords[N_valid,4],

@@ -210,3 +210,55 @@ def test_more_than_32_views_is_rejected_loudly():
     coords = S.dense_coords((96, 96, 96), 4)[:1000]
     with pytest.raises(_lib.EpreconError):
         hip_run(coords, window["vol_origin_partial"][None], 0.04, feats, np.ascontiguousarray(kr), 1)
+
+
+def _host_path_scene(name):
+    import back_project_ref as R
+    return R.exact_scene(C=8, V=3) if name == "exact" else R.scene(lvl=1, V=3, C=6, B=2, n=(37, 37))
+
+
+def _host_paths(sc, mv, mode, channels_last, **kw):
+    """the result of every host path of one back-projection: blocking, queued, queued with the caller's own read, two halves"""
+    from eprecon_amd import _lib
+    from eprecon_amd import back_project as BP
+    feats = _dev(sc["feats"])
+    if channels_last:
+        feats = BP.to_channels_last(feats)
+    args = (_dev(sc["coords"]), _dev(sc["origin"]), sc["voxel_size"], feats, _dev(sc["kr"]), mv, mode)
+    out = {"run": BP.run(*args, **kw), "run_async": BP.run_async(*args, **kw).result()}
+    held = BP.run_async(*args, hold_read=True, **kw)
+    out["hold_read"] = held.result_from(_lib.read_counts(held.n_valid_dev))
+    if channels_last:
+        counted = BP.count_async(args[0], args[1], args[2], tuple(feats.shape), args[4], mv, mode)
+        out["two_halves"] = BP.run_async(*args, counted=counted, **kw).result()
+    return out
+
+
+@pytest.mark.parametrize("channels_last", [False, True], ids=["nchw", "nhwc"])
+@pytest.mark.parametrize("mode", [0, 1, 2], ids=["mean", "mean_depth", "variance"])
+@pytest.mark.parametrize("name,mv", [("exact", 1), ("exact", 0), ("ragged_b2", 1)])
+def test_host_paths_give_the_same_bytes(name, mv, mode, channels_last):
+    """run, run_async + result, run_async(hold_read) + result_from and count_async + run_async(counted) build their result from
+    the same tensors: every key equal byte for byte (mv = 0 with one batch element: run's branch that waits for nothing)"""
+    got = _host_paths(_host_path_scene(name), mv, mode, channels_last, want_grid=True, want_mean=mode == 2)
+    ref = got.pop("run")
+    assert ref is not None and ref["n_valid"] > 0 and sum(ref["n_valid_per_batch"]) == ref["n_valid"]
+    assert set(ref) == {"feats", "coords", "count", "n_valid", "n_valid_per_batch", "grid", "mask"} | ({"mean"} if mode == 2 else set())
+    for path, res in got.items():
+        assert res is not None and set(res) == set(ref), path
+        for key, want in ref.items():
+            if torch.is_tensor(want):
+                assert res[key].dtype == want.dtype and res[key].shape == want.shape, (path, key)
+                assert res[key].cpu().numpy().tobytes() == want.cpu().numpy().tobytes(), (path, key)
+            else:
+                assert res[key] == want and type(res[key]) is type(want), (path, key)
+
+
+def test_host_paths_agree_on_a_batch_element_without_valid_voxels():
+    """every row of batch element 1 far outside every frustum: min_valid_per_batch = 1 makes each path return None"""
+    sc = dict(_host_path_scene("ragged_b2"))
+    sc["origin"] = sc["origin"].copy()
+    sc["origin"][1, 1] -= 1000.0      # (the float64 witness sees no row of element 1 in any view, none within 0.7 of a face)
+    for channels_last in (False, True):
+        got = _host_paths(sc, 1, 0, channels_last, min_valid_per_batch=1)
+        assert set(got) >= {"run", "run_async"} and all(v is None for v in got.values()), got
