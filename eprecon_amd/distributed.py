@@ -57,7 +57,7 @@ def _inside(c, lo, dim):
 
 class _Stamps:
     """Reference (torch) form of the per-voxel origin stamps, used by the CPU / gloo tests and the stateless wrapper; on the
-    GPU the stamps are a column of the map handle (csrc/global_map.hip) and no volume exists.
+    GPU the stamps are a column of the map handle (csrc/global_map_common.hpp) and no volume exists.
     Per scale: a dense int32 volume holding, for every voxel, the index of the fragment that produced its current features
     and whether this rank fused it itself: 0 = unknown, +(stamp + 1) = fused here, -(stamp + 1) = received.
     The volume is anchored at the first voxels it sees (lower corner minus a margin) and GROWS when a later voxel falls

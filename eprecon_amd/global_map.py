@@ -1,5 +1,5 @@
-"""Persistent sparse global map of GRU fusion: Python face of the eprecon_map_* handle
-(csrc/global_map.hip), the one stateful object of the C ABI (SURVEY.md 8b "Ownership").
+"""Persistent sparse global map of GRU fusion: Python face of the eprecon_map_* handle (csrc/global_map.hip and its
+global_map_{exchange,target,stage}.hip), the one stateful object of the C ABI (SURVEY.md 8b "Ownership").
 
 Mirrors the state the reference keeps in GRUFusion.global_volume[scale] / target_tsdf_volume[scale]
 (models/gru_fusion.py:31-38) and the per-fragment bookkeeping of convert2dense / update_map
@@ -11,6 +11,16 @@ import ctypes
 import torch
 
 from . import _lib
+
+
+def _host_int3(xyz):
+    return (ctypes.c_int32 * 3)(*[int(v) for v in xyz])     # a relative origin / box corner as the host int32[3] the C ABI reads
+
+
+def _gt_volumes(tsdf_gt, occ_gt):
+    """a fragment's dense ground truth as the twin's kernels read it: contiguous f32 TSDF, u8 occupancy (a bool mask is viewed)"""
+    occ_u8 = occ_gt.contiguous().view(torch.uint8) if occ_gt.dtype == torch.bool else occ_gt.to(torch.uint8).contiguous()
+    return tsdf_gt.to(torch.float32).contiguous(), occ_u8
 
 
 class GruStage:
@@ -56,8 +66,11 @@ class GlobalMap:
             except Exception:  # interpreter shutdown
                 pass
 
+    def _call(self, name, *args):
+        _lib.check(getattr(_lib.load(), name)(self._h, *args), name)
+
     def reset(self):
-        _lib.check(_lib.load().eprecon_map_reset(self._h), "eprecon_map_reset")
+        self._call("eprecon_map_reset")
 
     @property
     def size(self):
@@ -67,8 +80,7 @@ class GlobalMap:
         n = self.size
         c = torch.empty((n, 3), dtype=torch.int32, device=self.device)
         f = torch.empty((n, self.channels), dtype=torch.float32, device=self.device)
-        _lib.check(_lib.load().eprecon_map_export_async(self._h, _lib.ptr(c), _lib.ptr(f), _lib.current_stream()),
-                   "eprecon_map_export_async")
+        self._call("eprecon_map_export_async", _lib.ptr(c), _lib.ptr(f), _lib.current_stream())
         if self.on_read is not None:
             self.on_read()
         return c, f
@@ -89,13 +101,11 @@ class GlobalMap:
         coords = coords.to(device=self.device, dtype=torch.int32).contiguous()
         feats = feats.to(device=self.device, dtype=torch.float32).contiguous()
         assert coords.shape[0] == feats.shape[0] and feats.shape[1] == self.channels
-        _lib.check(_lib.load().eprecon_map_import_async(self._h, _lib.ptr(coords), _lib.ptr(feats), coords.shape[0],
-                                                        _lib.current_stream()), "eprecon_map_import_async")
+        self._call("eprecon_map_import_async", _lib.ptr(coords), _lib.ptr(feats), coords.shape[0], _lib.current_stream())
 
     def crop_union(self, cur_coords, cur_feat, dim, interval, rel, mode=0):
         """-> (updated int32[N',3], src_cur int32[N'], src_glob int32[N'], rows of the map inside the FBV).
         Blocking (one host read for N', where the reference's torch.nonzero synchronises too)."""
-        lib = _lib.load()
         n_cur = cur_feat.shape[0]
         assert cur_feat.stride(1) == 1 or n_cur == 0
         cur_coords = cur_coords.contiguous()     # raw pointers below: int32[N,4] rows
@@ -104,13 +114,12 @@ class GlobalMap:
         updated = torch.empty((cap, 3), dtype=torch.int32, device=dev)
         src_cur = torch.empty(cap, dtype=torch.int32, device=dev)
         src_glob = torch.empty(cap, dtype=torch.int32, device=dev)
-        rel_host = (ctypes.c_int32 * 3)(*[int(v) for v in rel])
+        rel_host = _host_int3(rel)
         counts = (ctypes.c_int64 * 2)()
         _lib.count_host_read()
-        _lib.check(lib.eprecon_map_crop_union(
-            self._h, _lib.ptr(cur_coords), _lib.ptr(cur_feat), n_cur, cur_feat.stride(0) if n_cur else self.channels,
-            dim, interval, int(mode), ctypes.cast(rel_host, ctypes.c_void_p), _lib.ptr(updated), _lib.ptr(src_cur),
-            _lib.ptr(src_glob), ctypes.cast(counts, ctypes.c_void_p), _lib.current_stream()), "eprecon_map_crop_union")
+        self._call("eprecon_map_crop_union", _lib.ptr(cur_coords), _lib.ptr(cur_feat), n_cur,
+                   cur_feat.stride(0) if n_cur else self.channels, dim, interval, int(mode), ctypes.cast(rel_host, ctypes.c_void_p),
+                   _lib.ptr(updated), _lib.ptr(src_cur), _lib.ptr(src_glob), ctypes.cast(counts, ctypes.c_void_p), _lib.current_stream())
         n = int(counts[0])
         return updated[:n], src_cur[:n], src_glob[:n], int(counts[1])
 
@@ -143,11 +152,10 @@ class GlobalMap:
         d.map, d.target_map = self._h, (target_map._h if target_map is not None else None)
         d.cur_coords, d.cur_feat, d.n_cur, d.ld_cur = _lib.ptr(cur_coords), _lib.ptr(cur_feat), n_cur, (cur_feat.stride(0) if n_cur else c)
         d.dim, d.interval, d.activity_mode = int(dim), int(interval), int(mode)
-        d.rel[0], d.rel[1], d.rel[2] = (int(v) for v in rel)
+        d.rel[0], d.rel[1], d.rel[2] = _host_int3(rel)
         keep = [cur_coords, cur_feat, ws]
         if target_map is not None:
-            tg = tsdf_gt.to(torch.float32).contiguous()
-            og = occ_gt.contiguous().view(torch.uint8) if occ_gt.dtype == torch.bool else occ_gt.to(torch.uint8).contiguous()
+            tg, og = _gt_volumes(tsdf_gt, occ_gt)
             d.tsdf_gt, d.occ_gt = _lib.ptr(tg), _lib.ptr(og)
             keep += [tg, og]
         origin = origin.detach().to(torch.float32).reshape(3).contiguous()
@@ -168,28 +176,25 @@ class GlobalMap:
 
     def gather(self, src_glob, col0, channels, out, fill=0.0):
         """out[i] = map.F[src_glob[i], col0:col0+channels] (fill where src_glob[i] < 0); out may be a column slice"""
-        _lib.check(_lib.load().eprecon_map_gather_async(self._h, _lib.ptr(src_glob), src_glob.shape[0], int(col0),
-                                                        int(channels), float(fill), _lib.ptr(out), out.stride(0),
-                                                        _lib.current_stream()), "eprecon_map_gather_async")
+        self._call("eprecon_map_gather_async", _lib.ptr(src_glob), src_glob.shape[0], int(col0), int(channels), float(fill),
+                   _lib.ptr(out), out.stride(0), _lib.current_stream())
         return out
 
     def update(self, updated, values):
         """update_map (models/gru_fusion.py:195-215) after crop_union: rows inside the FBV are replaced by
         (updated + relative origin, values)"""
-        _lib.check(_lib.load().eprecon_map_update_async(self._h, _lib.ptr(updated), updated.shape[0], _lib.ptr(values),
-                                                        values.stride(0), _lib.current_stream()),
-                   "eprecon_map_update_async")
+        self._call("eprecon_map_update_async", _lib.ptr(updated), updated.shape[0], _lib.ptr(values), values.stride(0),
+                   _lib.current_stream())
 
     # ---- multi-GPU boundary exchange (eprecon_amd/distributed.py) ----
     def set_fragment(self, fragment_index):
         """global index of the fragment whose fusion the next update() appends (-1: rows carry no origin)"""
-        _lib.check(_lib.load().eprecon_map_set_fragment(self._h, int(fragment_index)), "eprecon_map_set_fragment")
+        self._call("eprecon_map_set_fragment", int(fragment_index))
 
     def stamps(self):
         """int32[size]: 0 unknown, +(fragment + 1) fused by this rank, -(fragment + 1) received"""
         out = torch.empty(self.size, dtype=torch.int32, device=self.device)
-        _lib.check(_lib.load().eprecon_map_stamps_async(self._h, _lib.ptr(out), None, 0, 0, _lib.current_stream()),
-                   "eprecon_map_stamps_async")
+        self._call("eprecon_map_stamps_async", _lib.ptr(out), None, 0, 0, _lib.current_stream())
         if self.on_read is not None:
             self.on_read()
         return out
@@ -197,39 +202,32 @@ class GlobalMap:
     def set_stamps(self, stamps=None, fill=None):
         src = None if stamps is None else stamps.to(device=self.device, dtype=torch.int32).contiguous()
         assert src is None or src.shape[0] == self.size
-        _lib.check(_lib.load().eprecon_map_stamps_async(self._h, None, _lib.ptr(src), int(fill is not None), int(fill or 0),
-                                                        _lib.current_stream()), "eprecon_map_stamps_async")
+        self._call("eprecon_map_stamps_async", None, _lib.ptr(src), int(fill is not None), int(fill or 0), _lib.current_stream())
 
     def select_boundary(self, boxes_lo, own_box, dim, count_out):
         """boxes_lo int32[n_boxes,3] on the device; count_out: a device int32 element that receives the number of rows"""
-        _lib.check(_lib.load().eprecon_map_select_boundary_async(self._h, _lib.ptr(boxes_lo), boxes_lo.shape[0], int(own_box), int(dim),
-                                                                 _lib.ptr(count_out), _lib.current_stream()),
-                   "eprecon_map_select_boundary_async")
+        self._call("eprecon_map_select_boundary_async", _lib.ptr(boxes_lo), boxes_lo.shape[0], int(own_box), int(dim),
+                   _lib.ptr(count_out), _lib.current_stream())
 
     def pack_boundary(self, payload, n_rows):
         """payload: f32 buffer with room for n_rows x (4 + channels)"""
-        _lib.check(_lib.load().eprecon_map_pack_boundary_async(self._h, _lib.ptr(payload), int(n_rows), _lib.current_stream()),
-                   "eprecon_map_pack_boundary_async")
+        self._call("eprecon_map_pack_boundary_async", _lib.ptr(payload), int(n_rows), _lib.current_stream())
 
     def merge_boundary(self, payload, n_rows, box_lo, dim):
         """-> number of rows appended (blocking)"""
-        lo = (ctypes.c_int32 * 3)(*[int(v) for v in box_lo])
+        lo = _host_int3(box_lo)
         added = ctypes.c_int64(0)
         _lib.count_host_read()
-        _lib.check(_lib.load().eprecon_map_merge_boundary(self._h, _lib.ptr(payload), int(n_rows), ctypes.cast(lo, ctypes.c_void_p),
-                                                          int(dim), ctypes.cast(ctypes.byref(added), ctypes.c_void_p),
-                                                          _lib.current_stream()), "eprecon_map_merge_boundary")
+        self._call("eprecon_map_merge_boundary", _lib.ptr(payload), int(n_rows), ctypes.cast(lo, ctypes.c_void_p), int(dim),
+                   ctypes.cast(ctypes.byref(added), ctypes.c_void_p), _lib.current_stream())
         return int(added.value)
 
     def target_fuse(self, tsdf_gt, occ_gt, dim, rel, updated):
         """ground-truth twin (1 channel): -> tsdf_target f32[N',1] at the union voxels; the map is updated"""
-        lib = _lib.load()
-        tsdf_gt = tsdf_gt.to(torch.float32).contiguous()
-        occ_u8 = occ_gt.contiguous().view(torch.uint8) if occ_gt.dtype == torch.bool else occ_gt.to(torch.uint8).contiguous()
+        tsdf_gt, occ_u8 = _gt_volumes(tsdf_gt, occ_gt)
         out = torch.empty((updated.shape[0], 1), dtype=torch.float32, device=self.device)
-        rel_host = (ctypes.c_int32 * 3)(*[int(v) for v in rel])
+        rel_host = _host_int3(rel)
         _lib.count_host_read()
-        _lib.check(lib.eprecon_map_target_fuse(self._h, _lib.ptr(tsdf_gt), _lib.ptr(occ_u8), dim,
-                                               ctypes.cast(rel_host, ctypes.c_void_p), _lib.ptr(updated), updated.shape[0],
-                                               _lib.ptr(out), _lib.current_stream()), "eprecon_map_target_fuse")
+        self._call("eprecon_map_target_fuse", _lib.ptr(tsdf_gt), _lib.ptr(occ_u8), dim, ctypes.cast(rel_host, ctypes.c_void_p),
+                   _lib.ptr(updated), updated.shape[0], _lib.ptr(out), _lib.current_stream())
         return out

@@ -6,7 +6,7 @@ scale), F f32[M,C]} plus its ground-truth TSDF twin (the reference's test path r
 models/neucon_network.py:488).  One fragment step (per batch element):
 
   relative origin -> union of current voxels and the in-FBV part of the map, raster order
-  (the map is a C-ABI handle, eprecon_amd/global_map.py + csrc/global_map.hip: index volumes + scan, no dense
+  (the map is a C-ABI handle, eprecon_amd/global_map.py + csrc/global_map*.hip: index volumes + scan, no dense
   feature volume, no per-fragment re-allocation) -> gather current / global
   rows -> aligned-camera coordinates -> ConvGRU on the voxel channels and ConvGRU on the image
   channels (eprecon_amd.modules.ConvGRU) -> write the fused rows back into the map.

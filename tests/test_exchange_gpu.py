@@ -1,4 +1,4 @@
-"""The boundary exchange's device side on the map handle (csrc/global_map.hip: select / pack / merge, stamps as a map column)
+"""The boundary exchange's device side on the map handle (csrc/global_map_exchange.hip: select / pack / merge, stamps as a map column)
 against a plain numpy restatement of the protocol of eprecon_amd/distributed.py — the schedule that emulates the sequential
 map updates of models/gru_fusion.py:195-215,275 across ranks.  The merge is fed the payload of a SYNTHETIC second (and third)
 rank at cfg4 map sizes: present / absent voxels, newer / older stamps, the same voxel from two senders, rows outside the box."""
