@@ -92,16 +92,10 @@ __device__ __forceinline__ int block_exclusive_rank(bool pred, int *wave_counts,
     return off + within;
 }
 
-// device-wide exclusive scan of int32 (kernel_map.hip); scratch holds ceil(n / 2048) int32
-int exclusive_scan_i32(const int32_t *in, int n, int32_t *out, int32_t *scratch, int32_t *total_dev,
-                       hipStream_t st);
-// the same with the live length on the device: min(n, *n_dev) (n_dev may be nullptr); launches are sized by n
-int exclusive_scan_i32_dn(const int32_t *in, int n, const int32_t *n_dev, int32_t *out, int32_t *scratch, int32_t *total_dev,
-                          hipStream_t st);
-
 // Several device regions filled with a 32-bit pattern each in ONE launch (instead of a hipMemsetAsync / clear kernel per
 // region): the prologues of the stage calls clear a handful of index volumes, counters and hash tables of a few MB each, and
 // every launch they do not need is ~5 us of a fragment's chain.  Regions: 4-byte aligned, sizes multiples of 4 bytes.
+// (fill.hip; the device-wide scan is declared in scan.hpp, tables and kernel maps in hashgrid.hpp)
 struct FillRegion {
     void *p;
     size_t bytes;
@@ -109,25 +103,11 @@ struct FillRegion {
 };
 constexpr int kMaxFillRegions = 12;
 int multi_fill(const FillRegion *regions, int count, hipStream_t st);
-// the three regions that reset an open-addressing table (header, keys = empty, values = int max): kernel_map.hip
-int table_clear_regions(void *table, uint32_t capacity, FillRegion *out3);
-
-// eprecon_kernel_map_self_async whose caller filled the map's upper half (offsets 14 .. 26) with -1 itself — the region
-// kernel_map_self_fill_region names, typically inside a multi_fill that resets other things too
-FillRegion kernel_map_self_fill_region(int32_t *nbr, int64_t n);
-int kernel_map_self_prefilled(const void *table, uint32_t capacity, const int32_t *coords, int64_t n, int stride, int32_t *nbr,
-                              void *stream);
 
 // eprecon_trilinear_map_async without hash probes (csrc/voxelize.hip): base_row[i] = row of point i's base voxel in the set whose
 // 3x3x3 kernel map nbr27 int32[27][m] is given; the corners are that voxel's neighbours at the offsets {0, +1}^3
 int trilinear_from_map(const float *points_xyzb, int64_t n, const int32_t *base_row, const int32_t *nbr27, int64_t m, int stride,
                        int32_t *idx8, float *weight8, void *stream);
-
-// eprecon_unique_coords_dn_async for callers inside the library: table_cleared = the caller reset the table itself (multi_fill);
-// status_copy (optional device int32): receives the table's status word from the call's last launch
-int unique_coords_dn(const int32_t *coords, int64_t n_cap, const int32_t *n_dev, int quantum, void *table, uint32_t capacity,
-                     int32_t *inverse, int32_t *unique_coords, int32_t *n_unique_dev, void *workspace, size_t workspace_bytes,
-                     bool table_cleared, int32_t *status_copy, void *stream);
 
 // A side stream of the library's own per caller stream, for entry points that issue two independent chains of small launches
 // (csrc/gru_stage_finish.hip): record ev_fork on the caller's stream and let `side` wait for it, issue the second chain on

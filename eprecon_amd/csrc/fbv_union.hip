@@ -9,7 +9,7 @@
 // ranks and the feature rows are gathered straight from the sparse inputs — same output, same
 // order, including the reference's quirk that a row whose every channel is exactly 0.0 does not
 // activate its voxel (models/gru_fusion.py:96).
-#include "common.hpp"
+#include "scan.hpp"
 
 namespace {
 using namespace ep;
@@ -106,7 +106,7 @@ extern "C" {
 size_t eprecon_fbv_union_workspace_bytes(int dim)
 {
     const size_t cells = (size_t)dim * dim * dim;
-    return 4 * align_up(cells * 4, 256) + align_up((size_t)ceil_div((int64_t)cells, 2048) * 4, 256) + 256;
+    return 4 * align_up(cells * 4, 256) + scan_scratch_bytes((int64_t)cells) + 256;
 }
 
 /*

@@ -198,7 +198,7 @@ int ep::ensure_crop(EpMap *m, int dim)
         EP_HIP_CHECK(hipMalloc(&m->keep_rank, (size_t)cap * sizeof(int32_t)));
         m->row_cap = cap;
     }
-    const int64_t need = ceil_div(scan_n > rows ? scan_n : rows, 2048) + 8;
+    const int64_t need = scan_scratch_ints(scan_n > rows ? scan_n : rows) + 8;
     if (need > m->scratch_cap) {
         if (m->scan_scratch) EP_HIP_CHECK(hipFree(m->scan_scratch));
         EP_HIP_CHECK(hipMalloc(&m->scan_scratch, (size_t)need * 2 * sizeof(int32_t)));
@@ -231,7 +231,7 @@ int ep::ensure_sel(EpMap *m, int64_t rows)
         EP_HIP_CHECK(hipMalloc(&m->sel_aux, (size_t)cap * sizeof(int32_t)));
         m->sel_cap = cap;
     }
-    const int64_t need = ceil_div(rows, 2048) + 8;
+    const int64_t need = scan_scratch_ints(rows) + 8;
     if (need > m->sel_scratch_cap) {
         if (m->sel_scratch) EP_HIP_CHECK(hipFree(m->sel_scratch));
         EP_HIP_CHECK(hipMalloc(&m->sel_scratch, (size_t)need * sizeof(int32_t)));

@@ -2,7 +2,7 @@
 // A kernel lives in ONE unit; the host steps below are hidden and the inline helpers static, so `nm -D` shows none of this.
 #pragma once
 
-#include "common.hpp"
+#include "scan.hpp"
 
 #define EP_MAP_LOCAL __attribute__((visibility("hidden")))
 

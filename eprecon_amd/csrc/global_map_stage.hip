@@ -1,5 +1,6 @@
 // One GRU-fusion level queued as ONE call with device-side counts (include/eprecon_hip.h: eprecon_gru_stage_desc).
 #include "global_map_common.hpp"
+#include "hashgrid.hpp"
 
 namespace {
 using namespace ep;

@@ -7,7 +7,7 @@
 #include <mutex>
 #include <vector>
 
-#include "common.hpp"
+#include "hashgrid.hpp"
 
 namespace ep {
 // The two voxelisations are independent chains of small launches (lists, kernel map, ten-launch radix sort each): the second
@@ -72,7 +72,7 @@ int eprecon_gru_stage_finish_async(const eprecon_gru_finish_desc *d, void *strea
     // ordered before the caller's later work either way, and the first error is what the call returns.
     auto second = [&]() -> int {  // ---- second voxelisation: side stream ----
         EP_STEP(eprecon_segment_lists_async(d->inverse2, d->n, d->m2, d->offsets2, d->order2, ws_b, half, side));
-        if (d->m2 > 0) EP_STEP(ep::kernel_map_self_prefilled(d->table2, d->table_capacity, d->uniq2, d->m2, 1, d->nbr2, side));
+        if (d->m2 > 0) EP_STEP(ep::kernel_map_self(d->table2, d->table_capacity, d->uniq2, d->m2, 1, d->nbr2, true, side));
         if (d->literal)
             EP_STEP(eprecon_sphash_order_async(d->uniq2, d->m2, d->perm2, d->rank2, ws_b, half, side));
         else
@@ -82,7 +82,7 @@ int eprecon_gru_stage_finish_async(const eprecon_gru_finish_desc *d, void *strea
     };
     auto first = [&]() -> int {  // ---- first voxelisation: the caller's stream ----
         EP_STEP(eprecon_segment_lists_async(d->inverse1, d->n, d->m1, d->offsets1, d->order1, ws_a, half, stream));
-        if (d->m1 > 0) EP_STEP(ep::kernel_map_self_prefilled(d->table1, d->table_capacity, d->uniq1, d->m1, 1, d->nbr1, stream));
+        if (d->m1 > 0) EP_STEP(ep::kernel_map_self(d->table1, d->table_capacity, d->uniq1, d->m1, 1, d->nbr1, true, stream));
         // (corners from the set's kernel map and the numbering's inverse: no hash probes, ep::trilinear_from_map)
         EP_STEP(d->m1 > 0 ? ep::trilinear_from_map(d->scaled1, d->n, d->inverse1, d->nbr1, d->m1, 1, d->idx8_1, d->weight8_1, stream)
                           : eprecon_trilinear_map_async(d->table1, d->table_capacity, d->scaled1, d->n, 1, d->idx8_1, d->weight8_1, stream));

@@ -15,7 +15,7 @@
 #include <cstring>
 #include <string.h>
 
-#include "common.hpp"
+#include "scan.hpp"
 
 namespace {
 using namespace ep;
@@ -72,10 +72,11 @@ __global__ void bucket_rank_kernel(const unsigned long long *hash, const int32_t
 }
 
 // buckets = 2^bits with ~8 keys each, at most 32768 (the one-launch scan), at least 16
+constexpr int kMaxBucketBits = 15;
 int bucket_bits(int64_t n)
 {
     int bits = 4;
-    while (bits < 15 && ((int64_t)8 << bits) < n) ++bits;
+    while (bits < kMaxBucketBits && ((int64_t)8 << bits) < n) ++bits;
     return bits;
 }
 
@@ -88,6 +89,7 @@ size_t eprecon_sphash_order_workspace_bytes(int64_t n)
     if (n <= 0 || n > 0x7fffffff) return 0;
     const size_t nb = (size_t)1 << bucket_bits(n);
     // [hash | slot ids | count, cursor | start | scan scratch]
+    static_assert(scan_scratch_bytes(1 << kMaxBucketBits) <= 512, "the tail of the workspace is the scan's scratch");
     return align_up((size_t)n * 8, 256) + align_up((size_t)n * 4, 256) + 3 * align_up(nb * 4, 256) + 512;
 }
 

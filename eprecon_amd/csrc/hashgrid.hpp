@@ -11,6 +11,10 @@
 //   slot = mix64(key) & (capacity - 1), linear probing, capacity = power of two >= 2 * n
 //   value = smallest row index that inserted the key (atomicMin) -> duplicates collapse
 //           deterministically onto their first occurrence.
+//
+// A table's memory (table_bytes): a 256-byte header whose first int32 is the status word (bit 0: a key out of range, bit 1:
+// table full; the unique hierarchy keeps the level's count in the int32 behind it), then `capacity` 8-byte keys, then
+// `capacity` int32 values.  make_table / table_status are the one place that spells this out.
 #pragma once
 
 #include "common.hpp"
@@ -80,11 +84,43 @@ __device__ __forceinline__ int hash_lookup(const HashTable &t, unsigned long lon
     return -1;
 }
 
+constexpr size_t kTableHeaderBytes = 256;
+static inline size_t table_bytes(uint32_t capacity) { return kTableHeaderBytes + (size_t)capacity * 12; }
+// a power of two, at least 1024
+static inline bool table_capacity_ok(uint32_t c) { return c >= 1024 && (c & (c - 1)) == 0; }
+static inline HashTable make_table(const void *mem, uint32_t capacity)
+{
+    HashTable t;
+    t.keys = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(const_cast<void *>(mem)) + kTableHeaderBytes);
+    t.vals = reinterpret_cast<int32_t *>(t.keys + capacity);
+    t.mask = capacity - 1;
+    return t;
+}
+static inline int32_t *table_status(const void *mem) { return reinterpret_cast<int32_t *>(const_cast<void *>(mem)); }
+
 static inline uint32_t hash_capacity_for(int64_t n)
 {
     uint64_t c = 1024;
     while (c < (uint64_t)(2 * n + 1)) c <<= 1;
     return (uint32_t)c;
 }
+
+
+// the three regions that reset a table (header, keys = empty, values = int max) for ep::multi_fill: hash_unique.hip
+int table_clear_regions(void *table, uint32_t capacity, FillRegion *out3);
+
+// Unique voxel ids in first-occurrence order (hash_unique.hip): the body of eprecon_unique_coords_async / _dn_async.  n_dev
+// (optional, device): the live length is min(n_cap, *n_dev).  table_cleared: the caller reset the table itself (multi_fill);
+// status_copy (optional device int32): receives the table's status word from the call's last launch
+int unique_coords_dn(const int32_t *coords, int64_t n_cap, const int32_t *n_dev, int quantum, void *table, uint32_t capacity,
+                     int32_t *inverse, int32_t *unique_coords, int32_t *n_unique_dev, void *workspace, size_t workspace_bytes,
+                     bool table_cleared, int32_t *status_copy, void *stream);
+
+// The 3x3x3 map of a voxel set against its own table (kernel_map.hip): the body of eprecon_kernel_map_self_async.  prefilled: the
+// caller filled the map's upper half (offsets 14 .. 26) with -1 itself — the region kernel_map_self_fill_region names, typically
+// inside a multi_fill that resets other things too
+FillRegion kernel_map_self_fill_region(int32_t *nbr, int64_t n);
+int kernel_map_self(const void *table, uint32_t capacity, const int32_t *coords, int64_t n, int stride, int32_t *nbr, bool prefilled,
+                    void *stream);
 
 }  // namespace ep

@@ -24,7 +24,7 @@
 
 #include <mutex>
 
-#include "common.hpp"
+#include "scan.hpp"
 
 namespace {
 using namespace ep;
@@ -335,7 +335,7 @@ int eprecon_marching_cubes_table(int8_t *out_host)
 size_t eprecon_marching_cubes_workspace_bytes(int dx, int dy, int dz)
 {
     const size_t n = (size_t)dx * dy * dz;
-    return 4 * align_up(n * 4, 256) + 2 * align_up((size_t)ceil_div((int64_t)n, 2048) * 4, 256) + 256;
+    return 4 * align_up(n * 4, 256) + 2 * scan_scratch_bytes((int64_t)n) + 256;
 }
 
 }  // extern "C"
@@ -355,7 +355,7 @@ int mc_count(const float *volume, const float *weight, int dx, int dy, int dz, f
     if (rc != EPRECON_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     char *ws = reinterpret_cast<char *>(workspace);
-    const size_t seg = align_up((size_t)n * 4, 256), sseg = align_up((size_t)ceil_div(n, 2048) * 4, 256);
+    const size_t seg = align_up((size_t)n * 4, 256), sseg = scan_scratch_bytes(n);
     int32_t *nvert = reinterpret_cast<int32_t *>(ws), *ntri = reinterpret_cast<int32_t *>(ws + seg);
     int32_t *voff = reinterpret_cast<int32_t *>(ws + 2 * seg), *toff = reinterpret_cast<int32_t *>(ws + 3 * seg);
     int32_t *s1 = reinterpret_cast<int32_t *>(ws + 4 * seg), *s2 = reinterpret_cast<int32_t *>(ws + 4 * seg + sseg);

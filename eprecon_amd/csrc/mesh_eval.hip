@@ -21,7 +21,7 @@
 
 #include <algorithm>
 
-#include "common.hpp"
+#include "scan.hpp"
 
 namespace {
 using namespace ep;
@@ -538,7 +538,7 @@ size_t eprecon_voxel_down_sample_workspace_bytes(int64_t n, int64_t slab_cells)
 {
     if (n < 0 || slab_cells < 0) return 0;
     const size_t cseg = align_up((size_t)slab_cells * 4, 256);
-    return 3 * cseg + align_up((size_t)ceil_div(slab_cells, 2048) * 4, 256) + 256 + 2 * align_up((size_t)n * 4, 256) +
+    return 3 * cseg + scan_scratch_bytes(slab_cells) + 256 + 2 * align_up((size_t)n * 4, 256) +
            align_up((size_t)n * 24, 256);
 }
 
@@ -555,7 +555,7 @@ int eprecon_voxel_down_sample(const float *points, int64_t n, const double *min_
     if (workspace_bytes < eprecon_voxel_down_sample_workspace_bytes(n, slab_cells)) return EPRECON_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     char *ws = reinterpret_cast<char *>(workspace);
-    const size_t cseg = align_up((size_t)slab_cells * 4, 256), sseg = align_up((size_t)ceil_div(slab_cells, 2048) * 4, 256);
+    const size_t cseg = align_up((size_t)slab_cells * 4, 256), sseg = scan_scratch_bytes(slab_cells);
     int32_t *count = reinterpret_cast<int32_t *>(ws), *flag = reinterpret_cast<int32_t *>(ws + cseg),
             *slot = reinterpret_cast<int32_t *>(ws + 2 * cseg), *scratch = reinterpret_cast<int32_t *>(ws + 3 * cseg),
             *total = reinterpret_cast<int32_t *>(ws + 3 * cseg + sseg),
@@ -616,7 +616,7 @@ size_t eprecon_nn_search_workspace_bytes(int64_t n_ref, int64_t n_cells)
 {
     if (n_ref < 0 || n_cells < 0) return 0;
     const size_t cseg = align_up((size_t)n_cells * 4, 256);
-    return 3 * cseg + align_up((size_t)ceil_div(n_cells, 2048) * 4, 256) + 256 + align_up((size_t)n_ref * 16, 256);
+    return 3 * cseg + scan_scratch_bytes(n_cells) + 256 + align_up((size_t)n_ref * 16, 256);
 }
 
 int eprecon_nn_search_async(const float *ref, int64_t n_ref, const float *query, int64_t n_query, const double *lo_host,
@@ -632,7 +632,7 @@ int eprecon_nn_search_async(const float *ref, int64_t n_ref, const float *query,
     if (workspace_bytes < eprecon_nn_search_workspace_bytes(n_ref, n_cells)) return EPRECON_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     char *ws = reinterpret_cast<char *>(workspace);
-    const size_t cseg = align_up((size_t)n_cells * 4, 256), sseg = align_up((size_t)ceil_div(n_cells, 2048) * 4, 256);
+    const size_t cseg = align_up((size_t)n_cells * 4, 256), sseg = scan_scratch_bytes(n_cells);
     int32_t *count = reinterpret_cast<int32_t *>(ws), *start = reinterpret_cast<int32_t *>(ws + cseg),
             *cursor = reinterpret_cast<int32_t *>(ws + 2 * cseg), *scratch = reinterpret_cast<int32_t *>(ws + 3 * cseg),
             *total = reinterpret_cast<int32_t *>(ws + 3 * cseg + sseg);

@@ -124,14 +124,11 @@ extern "C" int eprecon_nearest_voxel_async(const void *table, uint32_t capacity,
                                            int64_t m, const int32_t *query_coords, int64_t n, int quantum,
                                            int32_t *out_index, void *stream)
 {
-    if (!table || capacity < 1024 || (capacity & (capacity - 1)) || m < 0 || n < 0 || quantum < 1 ||
+    if (!table || !table_capacity_ok(capacity) || m < 0 || n < 0 || quantum < 1 ||
         (m > 0 && !ref_coords) || (n > 0 && (!query_coords || !out_index)))
         return EPRECON_ERR_ARG;
     if (n == 0) return EPRECON_OK;
-    HashTable t;
-    t.keys = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(const_cast<void *>(table)) + 256);
-    t.vals = reinterpret_cast<int32_t *>(t.keys + capacity);
-    t.mask = capacity - 1;
+    const HashTable t = make_table(table, capacity);
     // offsets with |o|^2 <= kShellMax, ascending |o|^2: built once PER DEVICE under a lock (the pipelined serving mode
     // issues the panoptic branch from a worker thread: the first call may come from either thread), lives for the process
     static std::mutex shell_mutex;

@@ -2,7 +2,7 @@
 // host read has given the sizes of the three strided voxel sets: the point -> voxel CSR lists of strides 1 and 4, the two
 // k2s2 maps and their transposes, the three 3x3x3 kernel maps, the trilinear corner tables of strides 1 and 4.  Nothing new is
 // computed here: the call issues what the Python modules used to issue one by one (14 calls per pass).
-#include "common.hpp"
+#include "hashgrid.hpp"
 
 extern "C" {
 
@@ -37,12 +37,12 @@ int eprecon_spvcnn_geometry_async(const eprecon_spvcnn_geometry_desc *d, void *s
         if (d->n2 > 0) {
             EP_STEP(eprecon_kernel_map_async(d->table1, d->capacity1, d->coords2, d->n2, 2, 1, d->down12, side));
             EP_STEP(eprecon_transpose_map_async(d->coords1, d->n1, d->parent2, 1, d->up21, side));
-            EP_STEP(ep::kernel_map_self_prefilled(d->table2, d->capacity2, d->coords2, d->n2, 2, d->k2, side));
+            EP_STEP(ep::kernel_map_self(d->table2, d->capacity2, d->coords2, d->n2, 2, d->k2, true, side));
         }
         if (d->n4 > 0) {
             EP_STEP(eprecon_kernel_map_async(d->table2, d->capacity2, d->coords4, d->n4, 2, 2, d->down24, side));
             EP_STEP(eprecon_transpose_map_async(d->coords2, d->n2, d->parent4, 2, d->up42, side));
-            EP_STEP(ep::kernel_map_self_prefilled(d->table4, d->capacity4, d->coords4, d->n4, 4, d->k4, side));
+            EP_STEP(ep::kernel_map_self(d->table4, d->capacity4, d->coords4, d->n4, 4, d->k4, true, side));
             EP_STEP(eprecon_hash_query_async(d->table4, d->capacity4, d->vox, d->n, 4, d->idx4, side));
             EP_STEP(eprecon_segment_lists_async(d->idx4, d->n, d->n4, d->offsets4, d->order4, ws_b, half, side));
             // (corners from the set's kernel map and the points' stride-4 rows: no hash probes, ep::trilinear_from_map)
@@ -52,7 +52,7 @@ int eprecon_spvcnn_geometry_async(const eprecon_spvcnn_geometry_desc *d, void *s
     };
     auto unit = [&]() -> int {  // the stride-1 set: the caller's stream
         EP_STEP(eprecon_segment_lists_async(d->inverse1, d->n, d->n1, d->offsets1, d->order1, ws_a, half, stream));
-        EP_STEP(ep::kernel_map_self_prefilled(d->table1, d->capacity1, d->coords1, d->n1, 1, d->k1, stream));
+        EP_STEP(ep::kernel_map_self(d->table1, d->capacity1, d->coords1, d->n1, 1, d->k1, true, stream));
         EP_STEP(ep::trilinear_from_map(d->scaled, d->n, d->inverse1, d->k1, d->n1, 1, d->idx8_1, d->weight8_1, stream));
         return EPRECON_OK;
     };

@@ -12,6 +12,7 @@
 // (voxel, 4 channels) sums its points in index order -> deterministic, and the same lists serve
 // every later point_to_voxel on that voxel set.  All kernels are bandwidth/latency bound.
 #include "hashgrid.hpp"
+#include "scan.hpp"
 
 namespace {
 using namespace ep;
@@ -350,15 +351,6 @@ __global__ __launch_bounds__(256) void devoxelize_gate4_kernel(const float *feat
 
 __host__ inline bool vec4_ok(const void *p, int ld) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && (ld & 3) == 0; }
 
-HashTable make_table(const void *mem, uint32_t cap)
-{
-    HashTable t;
-    t.keys = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(const_cast<void *>(mem)) + 256);
-    t.vals = reinterpret_cast<int32_t *>(t.keys + cap);
-    t.mask = cap - 1;
-    return t;
-}
-
 // torchsparse's coordinate hash (F.sphash, ops/torchsparse_utils.py:19): FNV-1a over the four int32 of a row
 // in (x, y, z, batch) order, folded to 60 bits.  Needed only to reproduce the ORDER in which the
 // reference numbers voxels (`torch.unique(pc_hash)` = ascending hash), see remap_stale_index_kernel.
@@ -462,7 +454,7 @@ int eprecon_spvcnn_points_dn_async(const int32_t *src_coords, int64_t cap_src, c
 
 size_t eprecon_segment_workspace_bytes(int64_t n, int64_t m)
 {
-    return align_up((size_t)(m > 0 ? m : 1) * 4, 256) * 2 + align_up((size_t)ceil_div(m > 0 ? m : 1, 2048) * 4, 256) +
+    return align_up((size_t)(m > 0 ? m : 1) * 4, 256) * 2 + scan_scratch_bytes(m > 0 ? m : 1) +
            align_up((size_t)(n > 0 ? n : 1) * 4, 256) + 256;
 }
 
@@ -482,7 +474,7 @@ int eprecon_segment_lists_async(const int32_t *idx, int64_t n, int64_t m, int32_
     int32_t *counts = reinterpret_cast<int32_t *>(ws);
     int32_t *cursor = reinterpret_cast<int32_t *>(ws + seg);
     int32_t *scratch = reinterpret_cast<int32_t *>(ws + 2 * seg);
-    int32_t *unsorted = reinterpret_cast<int32_t *>(ws + 2 * seg + align_up((size_t)ceil_div(m, 2048) * 4, 256));
+    int32_t *unsorted = reinterpret_cast<int32_t *>(ws + 2 * seg + scan_scratch_bytes(m));
     EP_HIP_CHECK(hipMemsetAsync(counts, 0, 2 * seg, st));
     const dim3 gn((unsigned)ceil_div(n > 0 ? n : 1, 256)), blk(256);
     if (n > 0) {
@@ -522,7 +514,7 @@ int eprecon_segment_mean_async(const float *feat, int ld_feat, const int32_t *of
 int eprecon_trilinear_map_async(const void *table, uint32_t capacity, const float *points_xyzb, int64_t n,
                                 int stride, int32_t *idx8, float *weight8, void *stream)
 {
-    if (!table || capacity < 1024 || (capacity & (capacity - 1)) || n < 0 || stride < 1 ||
+    if (!table || !table_capacity_ok(capacity) || n < 0 || stride < 1 ||
         (n > 0 && (!points_xyzb || !idx8 || !weight8)))
         return EPRECON_ERR_ARG;
     if (n == 0) return EPRECON_OK;

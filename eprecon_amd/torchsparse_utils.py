@@ -1,5 +1,5 @@
 """Point <-> voxel glue of the point-voxel U-Net — mirror of ops/torchsparse_utils.py:15-105 on
-libeprecon_hip.so (csrc/voxelize.hip, csrc/kernel_map.hip)."""
+libeprecon_hip.so (csrc/voxelize.hip, csrc/hash_unique.hip, csrc/kernel_map.hip)."""
 import ctypes
 import os
 

@@ -191,3 +191,46 @@ def test_summary_rows_and_workspace_per_convolution_family(monkeypatch):
     monkeypatch.setenv("EPRECON_CONV_DENSE3D", "0")
     assert rows(_conv_desc(700, 27, 32, 1, **grid)) == _cdiv(700, 32)
     assert rows(_conv_desc(0, 27, 32, 32)) == 0 and ws(_conv_desc(0, 27, 96, 65, packed_weight=PACK)) == 0
+
+
+# lengths that straddle a scan tile (2,048) and the lengths at which the device scan changes its form (32,768; 4,096 tiles)
+_SCAN_EDGES = [0, 1, 2047, 2048, 2049, 32768, 32769, 8388608, 8388609]
+# the same products as three dimensions (2047 = 23 * 89, 2049 = 3 * 683, 32769 = 9 * 3641, 8388609 = 3 * 2796203)
+_SCAN_EDGE_DIMS = [(0, 1, 1), (1, 1, 1), (23, 89, 1), (16, 16, 8), (3, 683, 1), (32, 32, 32), (9, 3641, 1), (256, 256, 128),
+                   (3, 2796203, 1)]
+_SCAN_EDGE_CUBES = [0, 1, 12, 13, 16, 32, 33, 203, 204]        # dim^3 around 2,048, 32,768 and 8,388,608
+
+
+def _size_calls():
+    """(function, arguments) of every sizing call the golden file records"""
+    pairs = [(n, m) for n in _SCAN_EDGES for m in _SCAN_EDGES]
+    calls = {
+        "eprecon_hash_table_bytes": [(c,) for c in _SCAN_EDGES + [1024, 1 << 20, 1 << 31]],
+        "eprecon_unique_workspace_bytes": [(n,) for n in [-1] + _SCAN_EDGES],
+        "eprecon_gru_stage_workspace_bytes": [(n,) for n in _SCAN_EDGES],
+        "eprecon_sphash_order_workspace_bytes": [(n,) for n in _SCAN_EDGES],
+        "eprecon_marching_cubes_workspace_bytes": _SCAN_EDGE_DIMS,
+        "eprecon_fbv_union_workspace_bytes": [(d,) for d in _SCAN_EDGE_CUBES],
+        "eprecon_voxel_down_sample_workspace_bytes": pairs,
+        "eprecon_nn_search_workspace_bytes": pairs,
+        "eprecon_segment_workspace_bytes": pairs,
+        "eprecon_label_volumes_workspace_bytes": pairs,
+    }
+    return [(name, args) for name, arglist in calls.items() for args in arglist]
+
+
+def test_workspace_sizes_are_the_recorded_ones():
+    """Every sizing function that counts a scan scratch or a hash table returns what tests/golden/workspace_sizes.json
+    records (values taken from the build before the scratch size and the table layout got one definition each)."""
+    import json
+    import os
+    from eprecon_amd import _lib
+    lib = _lib.load()
+    golden = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "workspace_sizes.json")))
+    calls = _size_calls()
+    assert sorted(golden) == sorted({name for name, _ in calls})
+    assert sum(len(v) for v in golden.values()) == len(calls)
+    for name, args in calls:
+        want = golden[name][",".join(map(str, args))]
+        got = getattr(lib, name)(*args)
+        assert got == want, (name, args, got, want)

@@ -40,7 +40,7 @@ def test_device_scan_all_forms(monkeypatch, n):
     x = rng.integers(0, 9, n).astype(np.int32)
     want = np.concatenate([[0], np.cumsum(x[:-1], dtype=np.int64)]).astype(np.int32)
     dx = dev(x)
-    scratch = torch.empty((n + 2047) // 2048 + 1, dtype=torch.int32, device="cuda")
+    scratch = torch.empty((n + 2047) // 2048, dtype=torch.int32, device="cuda")
 
     def run():
         out = torch.full((n,), -7, dtype=torch.int32, device="cuda")
@@ -58,6 +58,28 @@ def test_device_scan_all_forms(monkeypatch, n):
         monkeypatch.setenv("EPRECON_SCAN_LOOKBACK", "0")
         got, tot = run()
         assert np.array_equal(got, want) and tot == int(x.sum())
+
+
+@pytest.mark.parametrize("n,lookback", [(32769, True), (32769, False), (4096 * 2048 + 1, True)])
+def test_device_scan_stays_inside_its_scratch(monkeypatch, n, lookback):
+    """the scratch is exactly the documented ceil(n / 2048) int32 with 64 guard words behind it, at the smallest length that
+    reaches each long form: the look-back launch (takes no scratch), tile sums + scan_apply<true> (17 tiles), and above 4,096
+    tiles tile sums + scan_sums_inplace + scan_apply<false> (4,097 tiles; the look-back does not go that far)"""
+    from eprecon_amd import _lib
+    lib = _lib.load()
+    if not lookback:
+        monkeypatch.setenv("EPRECON_SCAN_LOOKBACK", "0")
+    x = np.random.default_rng(n).integers(0, 9, n).astype(np.int32)
+    want = np.concatenate([[0], np.cumsum(x[:-1], dtype=np.int64)]).astype(np.int32)
+    tiles, guard = (n + 2047) // 2048, 0x5ca7c4ed
+    buf = torch.full((tiles + 64,), guard, dtype=torch.int32, device="cuda")
+    dx = dev(x)
+    out = torch.full((n,), -7, dtype=torch.int32, device="cuda")
+    tot = torch.full((1,), -7, dtype=torch.int32, device="cuda")
+    _lib.check(lib.eprecon_exclusive_scan_async(_lib.ptr(dx), n, _lib.ptr(out), _lib.ptr(tot), _lib.ptr(buf),
+                                                _lib.current_stream()), "eprecon_exclusive_scan_async")
+    assert bool((buf[tiles:] == guard).all())
+    assert np.array_equal(out.cpu().numpy(), want) and int(tot.item()) == int(x.sum()) < 2 ** 27
 
 
 def test_hash_rejects_out_of_range_keys():
