@@ -161,6 +161,92 @@ def count_async(coords, origin, voxel_size, feats_shape, krcam, min_view, mode=M
     return CountedBackProject(shape, inputs + (float(voxel_size), int(min_view), mode), count, n_valid_dev, ws, stream)
 
 
+class PreparedMaps:
+    """a level of prepare_levels_async without a list: `nhwc` is its maps [V, B, C, H, W] stored channels-last (inside `ws`
+    for NCHW input), valid for work that waits for `stream` (None: the stream the launch was queued on)"""
+
+    def __init__(self, nhwc, ws, stream):
+        self.nhwc, self.ws, self.stream = nhwc, ws, stream
+
+
+class PendingLevels:
+    """The gather halves of prepare_levels_async's levels — run_async(..., hd.nhwc, ..., hold_read=True, counted=hd) for every
+    handle hd — behind ONE pinned read of the tensor their counts are slices of (queued here: behind the last gather on the
+    current stream; the deferred checks pending there ride along).  results() -> what every PendingBackProject.result() would
+    have returned, one blocking read in all."""
+
+    def __init__(self, pends, handles):
+        self._pends, self._offsets, self._host = list(pends), [hd.n_valid_off for hd in handles], None
+        assert len(self._pends) == len(self._offsets) and all(hd.n_valid_all is handles[0].n_valid_all for hd in handles)
+        assert all(p.n_valid_dev.data_ptr() == hd.n_valid_dev.data_ptr() for p, hd in zip(self._pends, handles))
+        self._read = _lib.PinnedRead(handles[0].n_valid_all)
+
+    def results(self):
+        if self._host is None:
+            self._host = self._read.result()
+        return [p.result_from(self._host[o:o + 1 + p._batch]) for p, o in zip(self._pends, self._offsets)]
+
+
+def prepare_levels_async(levels, stream=None):
+    """Queue the first halves of up to four back-projections as ONE launch (eprecon_back_project_prepare_levels_async): per level
+    the re-layout of NCHW maps and the count.  levels: tuples (coords, origin, voxel_size, feats, krcam, min_view[, mode]) as
+    run_async takes them; coords None: the level's maps are re-laid out only.  stream: as for count_async.  Workspaces and counts
+    are the call's own; the counters of all levels are slices of one int32 tensor (`.n_valid_all`, from `.n_valid_off`).
+    -> one handle per level: a CountedBackProject hd whose `.nhwc` is the level's maps stored channels-last (inside its
+    workspace for NCHW input) — the gather half is run_async(coords, origin, voxel_size, hd.nhwc, krcam, min_view, mode,
+    counted=hd) — or a PreparedMaps for a level without a list.
+    EPRECON_BP_LEVELS=0: the same work, one launch per level."""
+    lib = _lib.load()
+    if not 1 <= len(levels) <= 4:
+        raise _lib.EpreconError("prepare_levels_async takes one to four levels")
+    dev = levels[0][3].device
+    rows = []
+    for lv in levels:
+        coords, origin, voxel_size, feats, krcam, min_view = lv[:6]
+        mode = lv[6] if len(lv) > 6 else MODE_MEAN
+        shape = tuple(int(x) for x in feats.shape)
+        feats_c, layout = _prep_feats(feats)
+        inputs = None if coords is None else _prep_inputs(coords, origin, krcam, shape[0], shape[1], dev)
+        rows.append((shape, feats_c, layout, inputs, float(voxel_size), int(min_view), mode))
+    n_valid_all = torch.empty((sum(1 + r[0][1] for r in rows if r[3] is not None),), dtype=torch.int32, device=dev)
+    descs = (_lib.BpLevel * len(rows))()
+    handles, off = [], 0
+    for d, (shape, feats_c, layout, inputs, voxel_size, min_view, mode) in zip(descs, rows):
+        v, b, c, h, w = shape
+        n = 0 if inputs is None else inputs[0].shape[0]
+        # buffers of the call's own, not the stream's grow-only scratch: they have to survive until the gather halves have run
+        ws = torch.empty((lib.eprecon_back_project_workspace_bytes(n, b, v, c, h, w, layout),), dtype=torch.uint8, device=dev)
+        d.n, d.batch, d.voxel_size, d.feats, d.feats_layout = n, b, voxel_size, feats_c.data_ptr(), layout
+        d.n_views, d.channels, d.height, d.width, d.min_view, d.mode = v, c, h, w, min_view, mode
+        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+        nhwc = feats_c
+        if layout == LAYOUT_NCHW:
+            o = lib.eprecon_back_project_workspace_maps_offset(n, b)
+            nhwc = ws[o:o + 4 * v * b * c * h * w].view(torch.float32).view(v, b, h, w, c).permute(0, 1, 4, 2, 3)
+        if inputs is None:
+            handles.append(PreparedMaps(nhwc, (ws, feats_c), stream))
+            continue
+        count = torch.empty((n,), dtype=torch.float32, device=dev)
+        n_valid_dev = n_valid_all[off:off + 1 + b]
+        d.coords, d.origin, d.krcam = (x.data_ptr() for x in inputs)
+        d.count, d.n_valid_dev = count.data_ptr(), n_valid_dev.data_ptr()
+        hd = CountedBackProject(shape, inputs + (voxel_size, min_view, mode), count, n_valid_dev, ws, stream)
+        hd.nhwc, hd.feats, hd.n_valid_all, hd.n_valid_off = nhwc, feats_c, n_valid_all, off
+        handles.append(hd)
+        off += 1 + b
+
+    def queue():
+        _lib.check(lib.eprecon_back_project_prepare_levels_async(ctypes.byref(descs), len(rows), _lib.current_stream()),
+                   "eprecon_back_project_prepare_levels_async")
+    if stream is None:
+        queue()
+    else:
+        stream.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(stream):
+            queue()
+    return handles
+
+
 def run_async(coords, origin, voxel_size, feats, krcam, min_view, mode=MODE_MEAN, min_valid_per_batch=1,
               want_grid=False, want_mean=False, hold_read=False, extra_words=0, rank_out=None, counted=None):
     """Queue the back-projection on the current stream and return a PendingBackProject.

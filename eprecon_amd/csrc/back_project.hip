@@ -701,6 +701,50 @@ __global__ __launch_bounds__(256) void bp_prepare_kernel(BpParams p, int32_t *ti
     }
 }
 
+// The prepare launches of several back-projections (levels) as ONE grid: the concatenation, level after level, of a level's re-layout
+// blocks and its count blocks.  A workgroup finds its level from block-uniform compares of its index against the levels' last
+// blocks (kernel arguments), then its half, and runs the body bp_prepare_kernel would have run with the level's own arguments:
+// the same tile totals, the same workspace, the same bits.  The levels do not depend on each other and nothing here waits for
+// another workgroup.  A channels-last level has no re-layout blocks, a level without a list no count blocks.
+constexpr int kMaxLevels = 4;
+struct BpLevelDev {
+    int end_relayout, end;   // one past the level's last re-layout block / last block in the concatenated grid
+    int vox, vec4, hw, tiles;
+    const float *in;
+    float *out;
+    int32_t *tile_sums, *blk_batch;
+    BpParams p;
+};
+struct BpLevelTable {
+    BpLevelDev lv[kMaxLevels];   // (slots behind the last level: end = the grid, so that no block selects them)
+};
+
+__global__ __launch_bounds__(256) void bp_prepare_levels_kernel(BpLevelTable t)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int bid = blockIdx.x;
+    int l = 0, begin = 0;
+#pragma unroll
+    for (int k = 0; k + 1 < kMaxLevels; ++k) {   // block-uniform
+        const int e = t.lv[k].end;
+        if (bid >= e) {
+            l = k + 1;
+            begin = e;
+        }
+    }
+    const BpLevelDev &L = t.lv[l];
+    if (bid < L.end_relayout) {
+        const int r = bid - begin, map = r / L.tiles, p0 = (r - map * L.tiles) * kTrPix;
+        if (L.vec4) relayout_body<true>(smem, L.in, L.out, L.p.C, L.hw, L.p.Cs, map, p0);
+        else relayout_body<false>(smem, L.in, L.out, L.p.C, L.hw, L.p.Cs, map, p0);
+    } else {
+        const int cb = bid - L.end_relayout;
+        if (L.vox == 256) count_body<256>(smem, L.p, L.tile_sums, L.blk_batch, cb);
+        else if (L.vox == 64) count_body<64>(smem, L.p, L.tile_sums, L.blk_batch, cb);
+        else count_body<16>(smem, L.p, L.tile_sums, L.blk_batch, cb);
+    }
+}
+
 // dynamic LDS of a gather workgroup: 12 (mlp: two weights and an offset) or 8 (pixel coordinates) bytes per (voxel, view), the
 // matrices, 3 or 5 words per voxel, sWave and sFold
 size_t gather_lds_bytes(bool mlp, int vox, int V, int B)
@@ -919,6 +963,112 @@ int bp_async_impl(BpArgs a)
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// eprecon_back_project_prepare_levels_async (host)
+// ---------------------------------------------------------------------------------------------
+BpArgs level_args(const eprecon_bp_level &lv, void *stream)
+{
+    return {EPRECON_BP_COUNT, lv.coords, lv.n, lv.origin, lv.batch, lv.voxel_size, lv.feats, lv.feats_layout, lv.krcam, lv.n_views,
+            lv.channels, lv.height, lv.width, lv.min_view, lv.mode, nullptr, nullptr, nullptr, lv.count, nullptr, nullptr,
+            lv.n_valid_dev, lv.workspace, lv.workspace_bytes, stream, nullptr};
+}
+
+// what bp_validate asks of a count half, for maps of either layout; a level without a list (coords == NULL) has its maps re-laid
+// out into the workspace, where a list of n entries leaves them, and needs neither counters nor matrices
+int bp_validate_level(BpArgs &a, bool listed)
+{
+    if (a.feats_layout != EPRECON_LAYOUT_NCHW && a.feats_layout != EPRECON_LAYOUT_NHWC) return EPRECON_ERR_ARG;
+    if (listed && a.feats_layout == EPRECON_LAYOUT_NHWC && !a.feats) a.feats = a.krcam;   // (not read by a count)
+    if (a.n < 0 || a.n > 0x7fffffff / 64 || a.batch <= 0 || a.n_views <= 0 || a.n_views > 32 || a.channels <= 0 ||
+        a.height <= 1 || a.width <= 1 || a.mode < 0 || a.mode > 2)
+        return EPRECON_ERR_ARG;
+    if (!a.feats || !a.workspace) return EPRECON_ERR_ARG;
+    if (listed && (!a.origin || !a.krcam || !a.n_valid_dev || (a.n > 0 && !a.count))) return EPRECON_ERR_ARG;
+    if ((size_t)a.n_views * a.batch * 12 * sizeof(float) > 32 * 1024) return EPRECON_ERR_UNSUPPORTED;
+    if (a.workspace_bytes < eprecon_back_project_workspace_bytes(a.n, a.batch, a.n_views, a.channels, a.height, a.width,
+                                                                 a.feats_layout))
+        return EPRECON_ERR_WORKSPACE;
+    if ((size_t)a.n_views * a.batch * a.channels * a.height * a.width > 0x7fffffffull) return EPRECON_ERR_UNSUPPORTED;
+    return EPRECON_OK;
+}
+
+int bp_prepare_levels_impl(const eprecon_bp_level *levels, int n_levels, hipStream_t st)
+{
+    if (!levels || n_levels <= 0 || n_levels > kMaxLevels) return EPRECON_ERR_ARG;
+    BpArgs args[kMaxLevels];
+    BpPlan plans[kMaxLevels];
+    bool listed[kMaxLevels];
+    for (int l = 0; l < n_levels; ++l) {
+        args[l] = level_args(levels[l], st);
+        listed[l] = levels[l].coords != nullptr;
+        const int rc = bp_validate_level(args[l], listed[l]);
+        if (rc != EPRECON_OK) return rc;
+        plans[l] = bp_plan(args[l]);
+        if (plans[l].nchw && plans[l].lds_relayout > 64 * 1024) return EPRECON_ERR_UNSUPPORTED;
+    }
+    // EPRECON_BP_LEVELS=0 (read per call), and the four-launch chain of EPRECON_BP_FOLD=0: every level's own launches, as the
+    // one-level call queues them
+    if (!eprecon_bp_levels() || plans[0].chain4) {
+        for (int l = 0; l < n_levels; ++l) {
+            const BpArgs &a = args[l];
+            const BpPlan &pl = plans[l];
+            int rc = EPRECON_OK;
+            if (listed[l]) rc = pl.vox == 256 ? bp_queue_count<256>(a, pl) : (pl.vox == 64 ? bp_queue_count<64>(a, pl) : bp_queue_count<16>(a, pl));
+            else if (pl.nchw)
+                rc = eprecon_nchw_to_nhwc_async(a.feats, pl.nhwc, a.n_views * a.batch, a.channels, a.height * a.width, st);
+            if (rc != EPRECON_OK) return rc;
+        }
+        return EPRECON_OK;
+    }
+    BpLevelTable t;
+    size_t lds = 0;
+    int cursor = 0;
+    for (int l = 0; l < kMaxLevels; ++l) {
+        BpLevelDev &d = t.lv[l];
+        d = BpLevelDev{};
+        if (l < n_levels) {
+            const BpArgs &a = args[l];
+            const BpPlan &pl = plans[l];
+            const bool count = listed[l] && a.n > 0;     // (an empty list: the counters are cleared, nothing else runs)
+            if (listed[l] && a.n == 0)
+                EP_HIP_CHECK(hipMemsetAsync(a.n_valid_dev, 0, sizeof(int32_t) * (size_t)(1 + a.batch), st));
+            d.hw = a.height * a.width;
+            d.tiles = ep::ceil_div(d.hw, kTrPix);
+            d.vox = pl.vox;
+            d.vec4 = relayout_vec4(a.feats, pl.nhwc, d.hw, pl.p.Cs) ? 1 : 0;
+            d.in = a.feats; d.out = pl.nhwc; d.tile_sums = pl.tile_sums; d.blk_batch = pl.blk_batch;
+            d.p = pl.p;
+            const bool relayout = pl.nchw && (count || !listed[l]);
+            if (relayout) {
+                cursor += d.tiles * a.n_views * a.batch;
+                lds = pl.lds_relayout > lds ? pl.lds_relayout : lds;
+            }
+            d.end_relayout = cursor;
+            if (count) {
+                cursor += pl.nblk_count;
+                lds = pl.lds_count > lds ? pl.lds_count : lds;
+            }
+        } else {
+            d.end_relayout = cursor;
+        }
+        d.end = cursor;
+    }
+    if (cursor > 0) {
+        hipLaunchKernelGGL(bp_prepare_levels_kernel, dim3((unsigned)cursor), dim3(256), lds, st, t);
+        EP_LAUNCH_CHECK();
+    }
+    for (int l = 0; l < n_levels; ++l) {   // lists of more tiles than EPRECON_BP_FOLD: the scan launch of the one-level call
+        const BpArgs &a = args[l];
+        const BpPlan &pl = plans[l];
+        if (listed[l] && a.n > 0 && !pl.p.fold) {
+            hipLaunchKernelGGL(bp_scan_kernel, dim3(1), dim3(1024), 0, st, pl.tile_sums, pl.ntile, a.n_valid_dev,
+                               (const int32_t *)pl.blk_batch, pl.nblk_count, a.batch);
+            EP_LAUNCH_CHECK();
+        }
+    }
+    return EPRECON_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -994,6 +1144,19 @@ int eprecon_back_project(const int32_t *coords, int64_t n, const float *origin, 
     for (int b = 0; b < batch; ++b)
         if (n_valid_host[1 + b] < min_valid_per_batch) return EPRECON_EMPTY;
     return EPRECON_OK;
+}
+
+size_t eprecon_back_project_workspace_maps_offset(int64_t n, int batch)
+{
+    return ep::align_up((size_t)ep::ceil_div(n, 16) * sizeof(int32_t), 256) +
+           ep::align_up((size_t)ep::ceil_div(n, 256) * batch * sizeof(int32_t), 256);
+}
+
+int eprecon_bp_levels(void) { return ep::switch_off("EPRECON_BP_LEVELS") ? 0 : 1; }
+
+int eprecon_back_project_prepare_levels_async(const eprecon_bp_level *levels, int n_levels, void *stream)
+{
+    return bp_prepare_levels_impl(levels, n_levels, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -66,6 +66,10 @@ class Cfg2Step:
         # (the three levels on their own stream: 1.57 ms, but the timed gather stretches to 142 us next to the 2D stack)
         self.bp_side_stream = False
         self._bp_stream = None
+        # the one prepare launch of the three levels in front of their gathers on the main stream (True, or
+        # EPRECON_BP_LEVELS_BESIDE=1: on the set-up side stream beside the 2D stack, where the step gains 12 us instead of 30:
+        # the 96^3 gather then finds its maps and list cold)
+        self.levels_beside_2d = False
 
     @torch.no_grad()
     def run(self):
@@ -91,7 +95,11 @@ class Cfg2Step:
         if select is not None:
             out["stage0_coords"], _ = select.result()
         for name in pending:
-            out[name] = pending[name].result()
+            if name == "_levels":     # the three levels behind one read of their counts (queue_levels)
+                names, read = pending[name]
+                out.update(zip(names, read.results()))
+            else:
+                out[name] = pending[name].result()
         self.last = out
         return out
 
@@ -101,10 +109,35 @@ class Cfg2Step:
         main = torch.cuda.current_stream(self.device)
         side = self._bp_stream if self.bp_side_stream else main
 
+        # The first halves of the three levels (re-layout of the maps, counts) need nothing of this step: they are ONE launch,
+        # and queue_levels queues it, the gathers and ONE read of the counts.  levels_beside_2d: that launch goes on the
+        # set-up side stream in front of the initialisation branch instead and runs beside the 2D stack.  Buffers are the call's own, so step k + 1's launch may be queued while step k's read is
+        # pending (defer_reads).
+        # (EPRECON_BP_LEVELS=0, bp_side_stream or levels_inside = False: every level's own launches and read, as before)
+        one_launch = self.levels_inside and not self.bp_side_stream and bool(_lib.load().eprecon_bp_levels())
+
+        def prepare_levels(stream):
+            return BP.prepare_levels_async(
+                [(self.coords[interval], self.origin, self.voxel_size, self.feats[lvl], self.krcam[lvl], mv)
+                 for _, lvl, interval, mv in LEVELS], stream=stream)
+        beside = self.levels_beside_2d or os.environ.get("EPRECON_BP_LEVELS_BESIDE", "0") == "1"
+        early = prepare_levels(_lib.side_stream(self.device, _lib.SIDE_SETUP)) if one_launch and beside else None
+
         def queue_levels():
             # The three dense Back_Project levels do not depend on the initialisation branch.  They are queued without a host
             # round trip between them (run_async) at the point where the initialisation branch has to wait for its valid-voxel
             # count: the GPU works through them while the host reads the count and starts issuing the submanifold stack.
+            if one_launch:
+                handles = early if early is not None else prepare_levels(None)
+                pends = []
+                for (name, lvl, interval, mv), hd in zip(LEVELS, handles):
+                    if self.profile_dominant and name == "bp96":
+                        _lib.load().eprecon_profile_enable(2)  # one-shot: bracket this level's gather kernel only
+                    # (hd.nhwc: the level's maps as the launch re-laid them out; the gather half takes channels-last maps)
+                    pends.append(BP.run_async(self.coords[interval], self.origin, self.voxel_size, hd.nhwc, self.krcam[lvl], mv,
+                                              hold_read=True, counted=hd))
+                pending["_levels"] = ([l[0] for l in LEVELS], BP.PendingLevels(pends, handles))
+                return
             if side is not main:
                 side.wait_stream(main)
             with torch.cuda.stream(side):

@@ -115,6 +115,36 @@ int eprecon_back_project_phase_async(int phase, const int32_t *coords, int64_t n
                                      void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * The first halves of up to four back-projections ("levels": the image pyramid's) as ONE launch: every level's re-layout of NCHW
+ * maps into its workspace and its count, for maps, lists and matrices that are all on the device already.  A level is what
+ * eprecon_back_project_phase_async takes, less the row outputs; its EPRECON_BP_GATHER half with the same arguments and workspace
+ * queues the level's second half, on this stream or on one that waits for it: a level of NCHW maps hands it the channels-last
+ * copy this launch made — `workspace` + eprecon_back_project_workspace_maps_offset(n, batch) bytes — as EPRECON_LAYOUT_NHWC
+ * maps.  coords == NULL: the level's maps are re-laid out only (no count; count / n_valid_dev / origin / krcam unused), to
+ * where a list of `n` entries puts them.  A channels-last level is counted only.  Every level's workspace holds exactly what its own
+ * eprecon_back_project_async call leaves there.  EPRECON_BP_LEVELS=0 (read at every call; eprecon_bp_levels() == 0): the
+ * same work as one launch per level, as eprecon_back_project_async queues it.
+ */
+typedef struct eprecon_bp_level {
+    const int32_t *coords;     /* int32[n,4], or NULL: re-layout only */
+    int64_t n;
+    const float *origin;       /* f32[batch,3] */
+    int32_t batch;
+    float voxel_size;
+    const float *feats;        /* f32[V,batch,C,H,W] or [V,batch,H,W,C] (feats_layout) */
+    int32_t feats_layout;
+    const float *krcam;        /* f32[V,batch,4,4] */
+    int32_t n_views, channels, height, width, min_view, mode;
+    float *count;              /* f32[n] */
+    int32_t *n_valid_dev;      /* int32[1 + batch], written by the level's gather half */
+    void *workspace;           /* the level's own, eprecon_back_project_workspace_bytes(...); lives until the gather half has run */
+    size_t workspace_bytes;
+} eprecon_bp_level;
+int eprecon_back_project_prepare_levels_async(const eprecon_bp_level *levels, int n_levels, void *stream);
+size_t eprecon_back_project_workspace_maps_offset(int64_t n, int batch);
+int eprecon_bp_levels(void);
+
+/*
  * For a list that IS the x-major raster of a dense grid (entry e = cell e, one batch element): the NEXT
  * eprecon_back_project_async / eprecon_back_project call of the calling host thread (or gather half) also writes rank int32[n + 1] —
  * rank[e] = output row of entry e or -1, rank[n] = 0 — which is the rank volume eprecon_grid_rank_async would build from
