@@ -859,11 +859,9 @@ BpPlan bp_plan(const BpArgs &a)
     p.min_view = a.min_view; p.out_feats = a.out_feats; p.out_mean = a.out_mean; p.out_coords = a.out_coords;
     p.count = a.count; p.out_grid = a.out_grid; p.out_mask = a.out_mask; p.n_valid_dev = a.n_valid_dev;
     p.block_offsets = pl.tile_sums; p.rank = a.rank;
-    {   // EPRECON_BP_XCD_SLABS=0 (read per call): the gather's tiles in hardware block order — round-robin over the eight XCDs, so
-        // every XCD's L2 sees tiles from the whole volume — instead of one contiguous slab of the raster per XCD.  Same results.
-        const char *e = getenv("EPRECON_BP_XCD_SLABS");
-        p.xcd_slabs = (e && e[0] == '0') ? 0 : 1;
-    }
+    // EPRECON_BP_XCD_SLABS=0 (read per call): the gather's tiles in hardware block order — round-robin over the eight XCDs, so
+    // every XCD's L2 sees tiles from the whole volume — instead of one contiguous slab of the raster per XCD.  Same results.
+    p.xcd_slabs = ep::switch_off("EPRECON_BP_XCD_SLABS") ? 0 : 1;
     pl.mlp = p.C % 4 == 0 && p.Cs % 4 == 0 && p.V <= 32 && (size_t)p.V * p.batch * p.H * p.W * p.Cs * 4 < 0x7fff0000ull &&
              gather_lds_bytes(true, 256, p.V, p.batch) <= dynamic_lds_limit();
 

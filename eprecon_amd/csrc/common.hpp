@@ -34,6 +34,12 @@ inline bool switch_off(const char *name)
     const char *e = getenv(name);
     return e && e[0] == '0';
 }
+// ... and one that defaults to off (an opt-in): NAME=1 turns it on
+inline bool switch_on(const char *name)
+{
+    const char *e = getenv(name);
+    return e && e[0] == '1';
+}
 
 // A run-time value picks a template argument: f (a generic lambda) gets, as a std::integral_constant, the X of the list that
 // equals x; the last X of the list takes every other value.

@@ -1,6 +1,7 @@
-// Direct gather form of the 3x3x3 sparse convolution: eligibility rule and dispatch.  The kernels and their launchers live in
-// sparse_conv_direct_impl.hpp and are instantiated per column-tile count by sparse_conv_direct_ct{1..4}.hip.
-#include "sparse_conv_direct_impl.hpp"
+// Direct gather form of the 3x3x3 sparse convolution: eligibility rule and dispatch.  The kernels (sparse_conv_direct_kernels.hpp,
+// sparse_conv_direct_persist.hpp) and their launcher (sparse_conv_direct_launch.hpp) are instantiated per column-tile count by
+// sparse_conv_direct_ct{1..4}.hip; this unit holds no kernel and shares only the selection rule with them.
+#include "sparse_conv_direct_select.hpp"
 
 namespace epconv {
 int launch_direct16_ct1(const ConvParams &p, hipStream_t st);

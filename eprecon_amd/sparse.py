@@ -353,7 +353,7 @@ def clear_packed_weights(module):
 
 
 # point-wise layers (K = 1) on lists at least this long take the direct kernel too (a streaming [N, C_in] x [C_in, C_out <= 64]
-# product: csrc/sparse_conv_direct_impl.hpp); shorter lists are launch-bound on any kernel
+# product: csrc/sparse_conv_direct_kernels.hpp); shorter lists are launch-bound on any kernel
 K1_DIRECT_MIN_ROWS = 20000
 
 
@@ -383,8 +383,8 @@ def _resolve_map(nbr, x, weight, desc, accumulate=False, ln=False, stats=False, 
         keep.append(pw)
     if nbr is not None and weight.shape[0] == 27 and weight.shape[2] <= DIRECT_MAX_COUT \
             and not accumulate and x.is_cuda:
-        # long lists: the direct gather kernel takes its B operands pre-packed (csrc/sparse_conv_direct_impl.hpp, spconv_direct16_kernel);
-        # which kernel runs is the library's choice, the packing only makes the direct one possible
+        # long lists: the direct gather kernel takes its B operands pre-packed (csrc/sparse_conv_direct_kernels.hpp,
+        # spconv_direct16_kernel); which kernel runs is the library's choice, the packing only makes the direct one possible
         pw = packed_weight16(weight)
         desc.packed_weight16 = pw.data_ptr()
         keep.append(pw)
