@@ -25,14 +25,11 @@ SIGNATURES = {
     "eprecon_back_project_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i, _i, _i]),
     "eprecon_back_project_async": (_i, [_vp, _i64, _vp, _i, _f, _vp, _i, _vp, _i, _i, _i, _i, _i, _i,
                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "eprecon_back_project": (_i, [_vp, _i64, _vp, _i, _f, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i,
-                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "eprecon_back_project_phase_async": (_i, [_i, _vp, _i64, _vp, _i, _f, _vp, _i, _vp, _i, _i, _i, _i, _i, _i,
-                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "eprecon_back_project_call_async": (_i, [_vp, _vp]),
+    "eprecon_back_project_call": (_i, [_vp, _i, _vp, _vp]),
     "eprecon_back_project_prepare_levels_async": (_i, [_vp, _i, _vp]),
     "eprecon_back_project_workspace_maps_offset": (_sz, [_i64, _i]),
     "eprecon_bp_levels": (_i, []),
-    "eprecon_back_project_rank_out": (_i, [_vp]),
     "eprecon_init_glue": (_i, []),
     "eprecon_profile_gather_kernel": (_c.c_char_p, []),
     "eprecon_hash_capacity": (_c.c_uint32, [_i64]),
@@ -259,13 +256,16 @@ class ViewsDesc(ctypes.Structure):
                 ("hw", ctypes.c_int32 * 3), ("levels", ctypes.c_int32), ("n_views", ctypes.c_int32)]
 
 
-class BpLevel(ctypes.Structure):
-    """include/eprecon_hip.h: eprecon_bp_level"""
+class BpCall(ctypes.Structure):
+    """include/eprecon_hip.h: eprecon_bp_call"""
     _fields_ = [("coords", ctypes.c_void_p), ("n", ctypes.c_int64), ("origin", ctypes.c_void_p), ("batch", ctypes.c_int32),
                 ("voxel_size", ctypes.c_float), ("feats", ctypes.c_void_p), ("feats_layout", ctypes.c_int32),
                 ("krcam", ctypes.c_void_p), ("n_views", ctypes.c_int32), ("channels", ctypes.c_int32), ("height", ctypes.c_int32),
                 ("width", ctypes.c_int32), ("min_view", ctypes.c_int32), ("mode", ctypes.c_int32), ("count", ctypes.c_void_p),
-                ("n_valid_dev", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)]
+                ("n_valid_dev", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
+                ("phase", ctypes.c_int32), ("out_feats", ctypes.c_void_p), ("out_mean", ctypes.c_void_p),
+                ("out_coords", ctypes.c_void_p), ("out_grid", ctypes.c_void_p), ("out_mask", ctypes.c_void_p),
+                ("rank", ctypes.c_void_p)]
 
 
 class GtCropDesc(ctypes.Structure):

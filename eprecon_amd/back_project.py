@@ -41,13 +41,6 @@ def dense_rank_buffer(coords, dims, interval):
     return torch.empty(coords.shape[0] + 1, dtype=torch.int32, device=coords.device)
 
 
-def _arm_rank(lib, rank_out, n, batch):
-    """the next library call of this thread writes the rank volume (eprecon_back_project_rank_out: one-shot)"""
-    if rank_out is not None:
-        assert batch == 1 and rank_out.dtype == torch.int32 and rank_out.is_contiguous() and rank_out.numel() == n + 1
-        _lib.check(lib.eprecon_back_project_rank_out(_lib.ptr(rank_out)), "eprecon_back_project_rank_out")
-
-
 def _prep_feats(feats):
     """feats: [V, B, C, H, W] (logical shape).  Channels-last storage (stride of C == 1) is passed
     through without a copy; anything else is made NCHW-contiguous."""
@@ -82,15 +75,26 @@ def _alloc_outputs(n, v, c, mode, want_grid, want_mean, dev, count=None):
             "mask": torch.empty((v * n,), dtype=torch.uint8, device=dev) if want_grid else None}
 
 
-def _lib_args(inputs, voxel_size, feats, layout, shape, min_view, mode, t, n_valid_dev, ws, extra=()):
-    """the argument tuple of eprecon_back_project_async (phase_async: behind the phase); t: _alloc_outputs(...) or, for the count
-    half, {"count": ...}; extra: what eprecon_back_project takes between `mode` and the outputs, and behind `n_valid_dev`"""
-    coords_i, origin_f, krcam_f = inputs
-    v, b, c, h, w = shape
-    p = lambda k: _lib.ptr(t.get(k))
-    return (_lib.ptr(coords_i), coords_i.shape[0], _lib.ptr(origin_f), b, float(voxel_size), _lib.ptr(feats), layout, _lib.ptr(krcam_f),
-            v, c, h, w, int(min_view), mode, *extra[:1], p("feats"), p("mean"), p("coords"), p("count"), p("grid"), p("mask"),
-            _lib.ptr(n_valid_dev), *extra[1:], _lib.ptr(ws), ws.numel(), _lib.current_stream())
+def _set_outputs(d, t, rank=None, phase=0):
+    """the outputs of a _lib.BpCall by field name; t: _alloc_outputs(...) or, for a count half, {"count": ...}; rank: `rank_out`"""
+    if rank is not None:
+        assert d.batch == 1 and rank.dtype == torch.int32 and rank.is_contiguous() and rank.numel() == d.n + 1
+    d.phase, d.count, d.rank = phase, _lib.ptr(t.get("count")), _lib.ptr(rank)
+    d.out_feats, d.out_mean, d.out_coords = _lib.ptr(t.get("feats")), _lib.ptr(t.get("mean")), _lib.ptr(t.get("coords"))
+    d.out_grid, d.out_mask = _lib.ptr(t.get("grid")), _lib.ptr(t.get("mask"))
+    return d
+
+
+def _call(inputs, feats, shape, layout, voxel_size, min_view, mode, t, n_valid_dev, ws, rank=None, phase=0, d=None):
+    """-> a _lib.BpCall (d: the one to fill) of these arguments, by field name.  inputs: _prep_inputs(...), or None for a level
+    without a list; t, rank, phase: _set_outputs.  The caller keeps every tensor alive: the descriptor holds plain addresses."""
+    d = _lib.BpCall() if d is None else d
+    if inputs is not None:
+        d.coords, d.origin, d.krcam = (_lib.ptr(x) for x in inputs)
+    d.n, d.voxel_size, d.feats, d.feats_layout = 0 if inputs is None else inputs[0].shape[0], float(voxel_size), _lib.ptr(feats), layout
+    d.n_views, d.batch, d.channels, d.height, d.width = shape
+    d.min_view, d.mode, d.n_valid_dev, d.workspace, d.workspace_bytes = int(min_view), mode, _lib.ptr(n_valid_dev), _lib.ptr(ws), ws.numel()
+    return _set_outputs(d, t, rank, phase)
 
 
 def _result(t, v, n_valid, per_batch, want_grid, want_mean, sliced=True):
@@ -129,15 +133,16 @@ class PendingBackProject:
 class CountedBackProject:
     """the count half of a back-projection (count_async), to be handed to run_async(counted=...) with the maps"""
 
-    def __init__(self, shape, inputs, count, n_valid_dev, ws, stream):
-        self.shape, self.inputs, self.count, self.n_valid_dev, self.ws, self.stream = shape, inputs, count, n_valid_dev, ws, stream
+    def __init__(self, shape, inputs, call, count, n_valid_dev, ws, stream):
+        self.shape, self.inputs, self.call, self.count = shape, inputs, call, count      # call: the _lib.BpCall that was queued
+        self.n_valid_dev, self.ws, self.stream = n_valid_dev, ws, stream
 
 
 def count_async(coords, origin, voxel_size, feats_shape, krcam, min_view, mode=MODE_MEAN, stream=None):
     """Queue the half of a back-projection that needs no maps — visible views per voxel, valid totals per tile — for
     channels-last maps of logical shape feats_shape = (V, B, C, H, W) that may not exist yet.  stream: another stream to
     queue it on behind the work queued so far (run_async waits for it); buffers are allocated on the current stream.
-    Same launches as the one-call form (eprecon_back_project_phase_async)."""
+    Same launches as the one-call form (eprecon_bp_call::phase)."""
     lib = _lib.load()
     dev = coords.device
     shape = v, b, c, h, w = tuple(int(x) for x in feats_shape)
@@ -148,17 +153,17 @@ def count_async(coords, origin, voxel_size, feats_shape, krcam, min_view, mode=M
     # a buffer of the call's own, not the stream's grow-only scratch: it has to survive until the gather half has run
     ws = torch.empty((lib.eprecon_back_project_workspace_bytes(n, b, v, c, h, w, LAYOUT_NHWC),), dtype=torch.uint8, device=dev)
 
+    call = _call(inputs, None, shape, LAYOUT_NHWC, voxel_size, min_view, mode, {"count": count}, n_valid_dev, ws, phase=1)
+
     def queue():
-        _lib.check(lib.eprecon_back_project_phase_async(
-            1, *_lib_args(inputs, voxel_size, None, LAYOUT_NHWC, shape, min_view, mode, {"count": count}, n_valid_dev, ws)),
-            "eprecon_back_project_phase_async")
+        _lib.check(lib.eprecon_back_project_call_async(ctypes.byref(call), _lib.current_stream()), "eprecon_back_project_call_async")
     if stream is None:
         queue()
     else:
         stream.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(stream):
             queue()
-    return CountedBackProject(shape, inputs + (float(voxel_size), int(min_view), mode), count, n_valid_dev, ws, stream)
+    return CountedBackProject(shape, inputs + (float(voxel_size), int(min_view), mode), call, count, n_valid_dev, ws, stream)
 
 
 class PreparedMaps:
@@ -209,16 +214,16 @@ def prepare_levels_async(levels, stream=None):
         inputs = None if coords is None else _prep_inputs(coords, origin, krcam, shape[0], shape[1], dev)
         rows.append((shape, feats_c, layout, inputs, float(voxel_size), int(min_view), mode))
     n_valid_all = torch.empty((sum(1 + r[0][1] for r in rows if r[3] is not None),), dtype=torch.int32, device=dev)
-    descs = (_lib.BpLevel * len(rows))()
+    descs = (_lib.BpCall * len(rows))()
     handles, off = [], 0
     for d, (shape, feats_c, layout, inputs, voxel_size, min_view, mode) in zip(descs, rows):
         v, b, c, h, w = shape
         n = 0 if inputs is None else inputs[0].shape[0]
         # buffers of the call's own, not the stream's grow-only scratch: they have to survive until the gather halves have run
         ws = torch.empty((lib.eprecon_back_project_workspace_bytes(n, b, v, c, h, w, layout),), dtype=torch.uint8, device=dev)
-        d.n, d.batch, d.voxel_size, d.feats, d.feats_layout = n, b, voxel_size, feats_c.data_ptr(), layout
-        d.n_views, d.channels, d.height, d.width, d.min_view, d.mode = v, c, h, w, min_view, mode
-        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+        count = None if inputs is None else torch.empty((n,), dtype=torch.float32, device=dev)
+        n_valid_dev = None if inputs is None else n_valid_all[off:off + 1 + b]
+        _call(inputs, feats_c, shape, layout, voxel_size, min_view, mode, {"count": count}, n_valid_dev, ws, d=d)
         nhwc = feats_c
         if layout == LAYOUT_NCHW:
             o = lib.eprecon_back_project_workspace_maps_offset(n, b)
@@ -226,11 +231,7 @@ def prepare_levels_async(levels, stream=None):
         if inputs is None:
             handles.append(PreparedMaps(nhwc, (ws, feats_c), stream))
             continue
-        count = torch.empty((n,), dtype=torch.float32, device=dev)
-        n_valid_dev = n_valid_all[off:off + 1 + b]
-        d.coords, d.origin, d.krcam = (x.data_ptr() for x in inputs)
-        d.count, d.n_valid_dev = count.data_ptr(), n_valid_dev.data_ptr()
-        hd = CountedBackProject(shape, inputs + (voxel_size, min_view, mode), count, n_valid_dev, ws, stream)
+        hd = CountedBackProject(shape, inputs + (voxel_size, min_view, mode), d, count, n_valid_dev, ws, stream)
         hd.nhwc, hd.feats, hd.n_valid_all, hd.n_valid_off = nhwc, feats_c, n_valid_all, off
         handles.append(hd)
         off += 1 + b
@@ -271,12 +272,13 @@ def run_async(coords, origin, voxel_size, feats, krcam, min_view, mode=MODE_MEAN
     else:
         n_valid_dev = torch.empty((1 + b + int(extra_words),), dtype=torch.int32, device=dev)
         ws = _lib.workspace(lib.eprecon_back_project_workspace_bytes(n, b, v, c, h, w, layout), dev)
-    _arm_rank(lib, rank_out, n, b)
-    args = _lib_args(inputs, voxel_size, feats_c, layout, shape, min_view, mode, t, n_valid_dev, ws)
-    if counted is not None:
-        _lib.check(lib.eprecon_back_project_phase_async(2, *args), "eprecon_back_project_phase_async")
+    if counted is not None:     # the descriptor of the count half, with the maps and the outputs
+        call = _lib.BpCall.from_buffer_copy(counted.call)
+        call.feats, call.feats_layout = _lib.ptr(feats_c), layout
+        _set_outputs(call, t, rank_out, phase=2)
     else:
-        _lib.check(lib.eprecon_back_project_async(*args), "eprecon_back_project_async")
+        call = _call(inputs, feats_c, shape, layout, voxel_size, min_view, mode, t, n_valid_dev, ws, rank_out)
+    _lib.check(lib.eprecon_back_project_call_async(ctypes.byref(call), _lib.current_stream()), "eprecon_back_project_call_async")
     read = None if hold_read else _lib.PinnedRead(n_valid_dev[:1 + b])
     # inputs stay referenced until result(): the kernels may still be reading them
     t["_keep"] = (*inputs, feats_c, n_valid_dev, ws if counted is not None else None)
@@ -298,23 +300,21 @@ def run(coords, origin, voxel_size, feats, krcam, min_view, mode=MODE_MEAN, min_
     t = _alloc_outputs(n, v, c, mode, want_grid, want_mean, dev)
     n_valid_dev = torch.empty((1 + b,), dtype=torch.int32, device=dev)
     ws = _lib.workspace(lib.eprecon_back_project_workspace_bytes(n, b, v, c, h, w, layout), dev)
+    call = _call(inputs, feats_c, shape, layout, voxel_size, min_view, mode, t, n_valid_dev, ws, rank_out)
 
     if min_view <= 0 and b == 1 and n >= max(int(min_valid_per_batch), 1):
         # every voxel is valid (the view count is never negative; the one batch element owns all rows): nothing to wait for.
         # The count is still produced on the device and checked with the level's next blocking read (a batch index out of
         # range is the one way a row can drop out).
-        _arm_rank(lib, rank_out, n, b)
-        _lib.check(lib.eprecon_back_project_async(
-            *_lib_args(inputs, voxel_size, feats_c, layout, shape, min_view, mode, t, n_valid_dev, ws)), "eprecon_back_project_async")
+        _lib.check(lib.eprecon_back_project_call_async(ctypes.byref(call), _lib.current_stream()), "eprecon_back_project_call_async")
         _lib.defer_check(n_valid_dev[0:1], n, "back-projection with min_view <= 0: rows with a batch index out of range")
         return _result(t, v, n, [n], want_grid, want_mean, sliced=False)
     n_valid_host = (ctypes.c_int32 * (1 + b))()
     _lib.count_host_read()
-    _arm_rank(lib, rank_out, n, b)
-    rc = lib.eprecon_back_project(*_lib_args(inputs, voxel_size, feats_c, layout, shape, min_view, mode, t, n_valid_dev, ws,
-                                             extra=(int(min_valid_per_batch), ctypes.cast(n_valid_host, ctypes.c_void_p))))
+    rc = lib.eprecon_back_project_call(ctypes.byref(call), int(min_valid_per_batch), ctypes.cast(n_valid_host, ctypes.c_void_p),
+                                       _lib.current_stream())
     _lib.drain_deferred()          # (the library copied the counts itself: pending checks are verified here, when there are any)
-    if not _lib.check(rc, "eprecon_back_project"):
+    if not _lib.check(rc, "eprecon_back_project_call"):
         return None
     return _result(t, v, int(n_valid_host[0]), [int(x) for x in n_valid_host[1:]], want_grid, want_mean)
 

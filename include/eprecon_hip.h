@@ -65,7 +65,7 @@ size_t eprecon_back_project_workspace_bytes(int64_t n, int batch, int n_views, i
                                             int height, int width, int feats_layout);
 
 /*
- * Stream-ordered; does not synchronise.
+ * One back-projection call, as a descriptor.  Every entry point below takes it; every pointer is device memory.
  *   coords      int32[n,4]            origin   f32[batch,3]       krcam f32[V,batch,4,4]
  *   out_feats   f32[n, C or C+1]      (first n_valid rows are written, input order preserved)
  *   out_mean    f32[n, C] or NULL     out_coords int32[n,4]       count f32[n] (visible views)
@@ -73,60 +73,16 @@ size_t eprecon_back_project_workspace_bytes(int64_t n, int batch, int n_views, i
  *   out_mask    u8 [V, n_valid]    or NULL   per-view visibility of the valid voxels
  *               (both packed with row stride n_valid, like the reference's im_grid / mask)
  *   n_valid_dev int32[1 + batch]      [0] = n_valid, [1 + b] = valid voxels of batch b
- */
-int eprecon_back_project_async(const int32_t *coords, int64_t n, const float *origin, int batch,
-                               float voxel_size, const float *feats, int feats_layout,
-                               const float *krcam, int n_views, int channels, int height,
-                               int width, int min_view, int mode, float *out_feats,
-                               float *out_mean, int32_t *out_coords, float *count,
-                               float *out_grid, uint8_t *out_mask, int32_t *n_valid_dev,
-                               void *workspace, size_t workspace_bytes, void *stream);
-
-/*
- * Blocking convenience: the call above, then copies n_valid_dev to n_valid_host[1 + batch] and
- * synchronises the stream (the reference synchronises at the same point: `torch.sum(valid_voxel)`
- * models/occupancy_initialization.py:231-233).  Returns EPRECON_EMPTY when some batch element
- * has fewer than `min_valid_per_batch` valid voxels (1 for Back_Project / back_project,
- * 1000 for the occupancy initialiser).
- */
-int eprecon_back_project(const int32_t *coords, int64_t n, const float *origin, int batch,
-                         float voxel_size, const float *feats, int feats_layout,
-                         const float *krcam, int n_views, int channels, int height, int width,
-                         int min_view, int mode, int min_valid_per_batch, float *out_feats,
-                         float *out_mean, int32_t *out_coords, float *count, float *out_grid,
-                         uint8_t *out_mask, int32_t *n_valid_dev, int32_t *n_valid_host,
-                         void *workspace, size_t workspace_bytes, void *stream);
-
-/*
- * eprecon_back_project_async in two halves, for channels-last maps (EPRECON_LAYOUT_NHWC) only.  EPRECON_BP_COUNT queues what
- * depends on the coordinates and matrices alone (count[], the tile totals in `workspace`; feats may be NULL); EPRECON_BP_GATHER
- * queues the rest.  Both take the same arguments and the same workspace, whose contents must survive in between; the count
- * half may run on another stream as long as it has finished when the gather half starts.  Count then gather on one stream
- * is the one-call form, launch for launch.
+ * phase: 0, the whole call, or one of its halves, for channels-last maps (EPRECON_LAYOUT_NHWC) only.  EPRECON_BP_COUNT queues
+ * what depends on the coordinates and matrices alone (count[], the tile totals in `workspace`; feats may be NULL, the row
+ * outputs and rank are ignored); EPRECON_BP_GATHER queues the rest.  Both take the same descriptor and the same workspace,
+ * whose contents must survive in between; the count half may run on another stream as long as it has finished when the
+ * gather half starts.  Count then gather on one stream is the whole call, launch for launch.
  */
 #define EPRECON_BP_COUNT 1
 #define EPRECON_BP_GATHER 2
-int eprecon_back_project_phase_async(int phase, const int32_t *coords, int64_t n, const float *origin, int batch,
-                                     float voxel_size, const float *feats, int feats_layout,
-                                     const float *krcam, int n_views, int channels, int height,
-                                     int width, int min_view, int mode, float *out_feats,
-                                     float *out_mean, int32_t *out_coords, float *count,
-                                     float *out_grid, uint8_t *out_mask, int32_t *n_valid_dev,
-                                     void *workspace, size_t workspace_bytes, void *stream);
-
-/*
- * The first halves of up to four back-projections ("levels": the image pyramid's) as ONE launch: every level's re-layout of NCHW
- * maps into its workspace and its count, for maps, lists and matrices that are all on the device already.  A level is what
- * eprecon_back_project_phase_async takes, less the row outputs; its EPRECON_BP_GATHER half with the same arguments and workspace
- * queues the level's second half, on this stream or on one that waits for it: a level of NCHW maps hands it the channels-last
- * copy this launch made — `workspace` + eprecon_back_project_workspace_maps_offset(n, batch) bytes — as EPRECON_LAYOUT_NHWC
- * maps.  coords == NULL: the level's maps are re-laid out only (no count; count / n_valid_dev / origin / krcam unused), to
- * where a list of `n` entries puts them.  A channels-last level is counted only.  Every level's workspace holds exactly what its own
- * eprecon_back_project_async call leaves there.  EPRECON_BP_LEVELS=0 (read at every call; eprecon_bp_levels() == 0): the
- * same work as one launch per level, as eprecon_back_project_async queues it.
- */
-typedef struct eprecon_bp_level {
-    const int32_t *coords;     /* int32[n,4], or NULL: re-layout only */
+typedef struct eprecon_bp_call {
+    const int32_t *coords;     /* int32[n,4] (a level of eprecon_back_project_prepare_levels_async: or NULL, re-layout only) */
     int64_t n;
     const float *origin;       /* f32[batch,3] */
     int32_t batch;
@@ -136,22 +92,57 @@ typedef struct eprecon_bp_level {
     const float *krcam;        /* f32[V,batch,4,4] */
     int32_t n_views, channels, height, width, min_view, mode;
     float *count;              /* f32[n] */
-    int32_t *n_valid_dev;      /* int32[1 + batch], written by the level's gather half */
-    void *workspace;           /* the level's own, eprecon_back_project_workspace_bytes(...); lives until the gather half has run */
+    int32_t *n_valid_dev;      /* int32[1 + batch], written by the gather half */
+    void *workspace;           /* eprecon_back_project_workspace_bytes(...); of the call's own while a gather half is outstanding */
     size_t workspace_bytes;
-} eprecon_bp_level;
-int eprecon_back_project_prepare_levels_async(const eprecon_bp_level *levels, int n_levels, void *stream);
-size_t eprecon_back_project_workspace_maps_offset(int64_t n, int batch);
-int eprecon_bp_levels(void);
+    int32_t phase;             /* 0, EPRECON_BP_COUNT or EPRECON_BP_GATHER */
+    float *out_feats, *out_mean;
+    int32_t *out_coords;
+    float *out_grid;
+    uint8_t *out_mask;
+    /* int32[n + 1] or NULL.  For a list that IS the x-major raster of a dense grid (entry e = cell e, one batch element): the
+     * gather also writes rank[e] = output row of entry e or -1, rank[n] = 0 — which is the rank volume eprecon_grid_rank_async
+     * would build from the call's out_coords (its trailing word counts voxels off the grid: none here).  An output of this call
+     * like the others: the count half ignores it, batch != 1 is EPRECON_ERR_ARG before any launch, n == 0 clears rank[0]. */
+    int32_t *rank;
+} eprecon_bp_call;
+
+/* Stream-ordered; does not synchronise.  The whole call or the half `phase` names. */
+int eprecon_back_project_call_async(const eprecon_bp_call *call, void *stream);
 
 /*
- * For a list that IS the x-major raster of a dense grid (entry e = cell e, one batch element): the NEXT
- * eprecon_back_project_async / eprecon_back_project call of the calling host thread (or gather half) also writes rank int32[n + 1] —
- * rank[e] = output row of entry e or -1, rank[n] = 0 — which is the rank volume eprecon_grid_rank_async would build from
- * the call's out_coords (its trailing word counts voxels off the grid: none here).  One-shot: that call takes the pointer
- * whatever it returns.  NULL disarms.
+ * Blocking convenience (phase 0 or EPRECON_BP_GATHER): the call above, then copies n_valid_dev to n_valid_host[1 + batch] and
+ * synchronises the stream (the reference synchronises at the same point: `torch.sum(valid_voxel)`
+ * models/occupancy_initialization.py:231-233).  Returns EPRECON_EMPTY when some batch element
+ * has fewer than `min_valid_per_batch` valid voxels (1 for Back_Project / back_project,
+ * 1000 for the occupancy initialiser).
  */
-int eprecon_back_project_rank_out(int32_t *rank);
+int eprecon_back_project_call(const eprecon_bp_call *call, int min_valid_per_batch, int32_t *n_valid_host, void *stream);
+
+/* The whole call with plain arguments, for callers without the struct: fills a descriptor (phase 0, no rank) and queues it. */
+int eprecon_back_project_async(const int32_t *coords, int64_t n, const float *origin, int batch,
+                               float voxel_size, const float *feats, int feats_layout,
+                               const float *krcam, int n_views, int channels, int height,
+                               int width, int min_view, int mode, float *out_feats,
+                               float *out_mean, int32_t *out_coords, float *count,
+                               float *out_grid, uint8_t *out_mask, int32_t *n_valid_dev,
+                               void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * The first halves of up to four back-projections ("levels": the image pyramid's) as ONE launch: every level's re-layout of NCHW
+ * maps into its workspace and its count, for maps, lists and matrices that are all on the device already.  A level is a call
+ * descriptor with a workspace of its own; `phase`, the row outputs and `rank` are ignored here.  The same descriptor with
+ * phase = EPRECON_BP_GATHER and the outputs filled in queues the level's second half, on this stream or on one that waits for
+ * it: a level of NCHW maps hands it the channels-last copy this launch made — `workspace` +
+ * eprecon_back_project_workspace_maps_offset(n, batch) bytes — as EPRECON_LAYOUT_NHWC maps.  coords == NULL: the level's maps
+ * are re-laid out only (no count; count / n_valid_dev / origin / krcam unused), to where a list of `n` entries puts them.  A
+ * channels-last level is counted only.  Every level's workspace holds exactly what its own eprecon_back_project_async call
+ * leaves there: the tile totals at offset 0, the per-batch rows, then the maps.  EPRECON_BP_LEVELS=0 (read at every call;
+ * eprecon_bp_levels() == 0): the same work as one launch per level, as eprecon_back_project_async queues it.
+ */
+int eprecon_back_project_prepare_levels_async(const eprecon_bp_call *levels, int n_levels, void *stream);
+size_t eprecon_back_project_workspace_maps_offset(int64_t n, int batch);
+int eprecon_bp_levels(void);
 
 /*
  * EPRECON_INIT_GLUE (read at every call): 1 unless the variable is set to 0.  0 keeps the occupancy-initialisation branch on

@@ -93,7 +93,7 @@ def test_operators_refuse_cpu_tensors():
                                             ("eprecon_mlp4x_head", "Mlp4xHead"), ("eprecon_mlp4x_desc", "Mlp4xDesc"),
                                             ("eprecon_gru_finish_desc", "GruFinishDesc"), ("eprecon_spvcnn_geometry_desc", "SpvcnnGeometryDesc"),
                                             ("eprecon_spvcnn_conv", "SpvcnnConv"), ("eprecon_spvcnn_bn", "SpvcnnBn"),
-                                            ("eprecon_spvcnn_forward_desc", "SpvcnnForwardDesc")])
+                                            ("eprecon_spvcnn_forward_desc", "SpvcnnForwardDesc"), ("eprecon_bp_call", "BpCall")])
 def test_struct_layouts_match_header(tmp_path, c_name, py_name):
     """the ctypes mirrors of the descriptor structs have the size and field offsets the C compiler gives the header's
     structs (a drift here would silently corrupt every launch that goes through them)"""
@@ -113,3 +113,33 @@ def test_struct_layouts_match_header(tmp_path, c_name, py_name):
     out = [int(x) for x in subprocess.check_output([str(exe)]).split()]
     assert out[0] == ctypes.sizeof(mirror)
     assert out[1:] == [getattr(mirror, name).offset for name in fields]
+
+
+def _bp_workspace_formula(n, batch, v, c, h, w, layout):
+    """include/eprecon_hip.h: the tile totals (one int32 per 16 voxels) at offset 0, the count workgroups' per-batch rows
+    (one int32 per 256 voxels and batch element), then the channels-last copy of NCHW maps: every part a multiple of 256
+    bytes.  -> (eprecon_back_project_workspace_bytes, eprecon_back_project_workspace_maps_offset)"""
+    up = lambda x: (x + 255) // 256 * 256
+    cdiv = lambda a, b: (a + b - 1) // b
+    carve = lambda n_, b_: up(cdiv(n_, 16) * 4) + up(cdiv(n_, 256) * b_ * 4)
+    maps = up(v * batch * c * h * w * 4) if layout == 0 else 0
+    return carve(max(n, 1), max(batch, 1)) + maps + 256, carve(n, batch)
+
+
+@pytest.mark.parametrize("layout", [0, 1])
+@pytest.mark.parametrize("shape", [(3, 8, 12, 16), (9, 24, 120, 160)])
+def test_back_project_workspace_table(lib, shape, layout):
+    """the two exported size functions of the back-projection against the layout restated above, at list lengths around the
+    16-voxel tile, the 256-voxel count workgroup and the two tile thresholds (48 K, 512 K); and the maps start where a
+    call's own carve ends when nothing is clamped (n, batch >= 1)"""
+    v, c, h, w = shape
+    for n in (0, 1, 15, 16, 17, 255, 256, 257, 49152, 524288):
+        for batch in (1, 2, 3):
+            want_bytes, want_off = _bp_workspace_formula(n, batch, v, c, h, w, layout)
+            got_bytes = lib.eprecon_back_project_workspace_bytes(n, batch, v, c, h, w, layout)
+            got_off = lib.eprecon_back_project_workspace_maps_offset(n, batch)
+            assert (got_bytes, got_off) == (want_bytes, want_off), (n, batch, shape, layout)
+            assert got_off % 256 == 0 and got_bytes % 256 == 0
+            if n >= 1:
+                maps = (v * batch * c * h * w * 4 + 255) // 256 * 256 if layout == 0 else 0
+                assert got_off + maps + 256 == got_bytes
