@@ -146,6 +146,11 @@ SIGNATURES = {
     "eprecon_voxel_down_sample": (_i, [_vp, _i64, _vp, _c.c_double, _vp, _vp, _vp, _i64, _vp, _sz, _vp]),
     "eprecon_nn_search_workspace_bytes": (_sz, [_i64, _i64]),
     "eprecon_nn_search_async": (_i, [_vp, _i64, _vp, _i64, _vp, _c.c_double, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "eprecon_label_transfer_workspace_bytes": (_sz, [_vp, _i64]),
+    "eprecon_label_bricks_async": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "eprecon_label_transfer_async": (_i, [_vp, _vp, _vp, _vp, _vp, _c.c_double, _vp, _i, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _sz,
+                                          _vp]),
+    "eprecon_instance_vote_async": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "eprecon_nearest_voxel_async": (_i, [_vp, _c.c_uint32, _vp, _i64, _vp, _i64, _i, _vp, _vp]),
     "eprecon_upsample2x_nhwc_async": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "eprecon_decoder_keys_async": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp]),

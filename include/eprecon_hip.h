@@ -938,6 +938,43 @@ int eprecon_nn_search_async(const float *ref, int64_t n_ref, const float *query,
                             size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Panoptic export: voxel labels onto mesh vertices  (tools/generate_semantic_instance.py)
+ *
+ * The sites are the cells of a dense label volume (semantic, instance int32[X,Y,Z], dims_host int32[3]) whose class
+ * maps to a non-zero id: mapping_host int32[n_map] (host memory, 1 <= n_map <= 256), site <=> mapping[semantic] != 0.
+ * A site's world coordinate per axis is fl64(fl64(i) * voxel_size) + fl64(origin_host[a]) (numpy's
+ * idx * voxel_size + origin with a float64 voxel size and a float32 origin); no cloud of them is ever built.
+ * More than 2^31 - 1 cells: EPRECON_ERR_UNSUPPORTED.
+ *
+ * eprecon_label_bricks_async: masks_out uint64[ceil(X/4) * ceil(Y/4) * ceil(Z/4)] (brick (bx, by, bz) at
+ *   (bx * BY + by) * BZ + bz), bit (x & 3) << 4 | (y & 3) << 2 | (z & 3) of a brick's word = that cell is a site (cells
+ *   outside the volume: 0).  status_out int32[2] on the device (cleared here): [0] != 0 when a semantic value lies outside
+ *   [0, n_map) (the masks are then not to be used), [1] the number of sites.
+ * eprecon_label_transfer_async: query f32[n_query,3] -> per vertex the nearest site in squared fp64 distance
+ *   (dx*dx + dy*dy) + dz*dz, every operation rounded on its own; among equal distances the smallest linear cell index
+ *   (x * Y + y) * Z + z.  idx_out int32 (that index), dist_out f32 (of the fp64 root), sem_out int32
+ *   (mapping[semantic[idx]]), ins_out int32 (instance[idx]); no site at all: -1, +inf, 0, 0.  One thread per vertex
+ *   walks its own brick and near_shells shells of bricks around it; a vertex not decided by then is queued on the
+ *   device and finished by one wave each (near_shells < 0: every vertex goes to the waves; near_shells > 2^30: none).
+ *   The result does not depend on the path.  n_query == 0 is a no-op.
+ *   workspace: eprecon_label_transfer_workspace_bytes(dims_host, n_query) (0 for an unsupported volume).
+ * eprecon_instance_vote_async: mapped_sem int32[n] in [0, n_class), rank int32[n] in [0, n_inst) -> per instance rank
+ *   class_out int32[n_inst] = the class with the most vertices, among equal counts the one whose first vertex has the
+ *   smallest index (CPython's Counter(...).most_common(1)), count_out int32[n_inst] = its vertices (all classes).
+ *   Integer atomics only.  workspace: n_inst * n_class * 8 bytes (+ 256); entries out of range are ignored.
+ * ------------------------------------------------------------------------------------------ */
+size_t eprecon_label_transfer_workspace_bytes(const int32_t *dims_host, int64_t n_query);
+int eprecon_label_bricks_async(const int32_t *semantic, const int32_t *dims_host, const int32_t *mapping_host, int n_map,
+                               uint64_t *masks_out, int32_t *status_out, void *stream);
+int eprecon_label_transfer_async(const uint64_t *masks, const int32_t *semantic, const int32_t *instance,
+                                 const int32_t *dims_host, const float *origin_host, double voxel_size,
+                                 const int32_t *mapping_host, int n_map, const float *query, int64_t n_query, int near_shells,
+                                 int32_t *idx_out, float *dist_out, int32_t *sem_out, int32_t *ins_out, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+int eprecon_instance_vote_async(const int32_t *mapped_sem, const int32_t *rank, int64_t n, int n_inst, int n_class,
+                                int32_t *class_out, int32_t *count_out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Nearest finest-level voxel  (K18)
  *
  * Replaces  torch.cdist + argmin(dim=1)                 models/mask3dformer.py:361-367
