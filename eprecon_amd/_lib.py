@@ -58,6 +58,7 @@ SIGNATURES = {
     "eprecon_conv_desc_async": (_i, [_vp, _vp]),
     "eprecon_exclusive_scan_async": (_i, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "eprecon_conv_desc_partial_rows": (_i64, [_vp]),
+    "eprecon_conv_dense3d_kind": (_i, [_vp]),
     "eprecon_bn_acc_words": (_sz, [_i]),
     "eprecon_conv_desc_takes_bn_acc": (_i, [_vp]),
     "eprecon_batchnorm_acc_affine_async": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp]),

@@ -302,7 +302,9 @@ inline bool gather_vec4(const ConvParams &p)
 
 // sparse_conv_dense3d.hip: the 3x3x3 stride-1 convolution on a dense grid (vox_rank), no kernel map
 enum D3Kind { kD3None = 0, kD3Narrow = 1, kD3Tile16 = 2 };
-int conv3d_kind(const ConvParams &p);                   // which of the two kernels takes the layer (EPRECON_CONV_DENSE3D)
+// which of the two kernels the layer's shape is for (EPRECON_CONV_DENSE3D); exported as eprecon_conv_dense3d_kind only
+__attribute__((visibility("hidden"))) int conv3d_shape_kind(const ConvParams &p);
+int conv3d_kind(const ConvParams &p);                   // ... and which takes the launch: the 16-row kernel needs its wq16 packing
 int d3_tiles_kind(const ConvParams &p, int kind, int *ty = nullptr, int *tz = nullptr);   // workgroups = BatchNorm summary rows
 int launch_conv3d_16(const ConvParams &p, hipStream_t st);
 int launch_conv3d_single_column(const ConvParams &p, hipStream_t st);
@@ -341,6 +343,10 @@ int direct16_partial_block_rows(const ConvParams &p);   // 128, or 32 when the p
 // sparse_conv_tile2d.hip: the dense 2D 3x3 layers of the fusion stack on the 16-row image-tile kernel
 // long pixel lists only (the rule dense2d.DIRECT_2D_MIN_ROWS hands the wq16 packing over by); shorter lists: the short-list kernel
 constexpr int kT2MinRows = 40000;
+// the two thresholds of the hand-over rule (eprecon_amd/sparse.py conv_packings) that the one-call SPVCNN pass needs at run
+// time, where alone its row counts exist (spvcnn_forward.hip): sparse.DIRECT_MAX_COUT and sparse.K1_DIRECT_MIN_ROWS
+constexpr int kDirectMaxCout = 64;
+constexpr int64_t kK1DirectMinRows = 20000;
 bool tile2d16_ok(const ConvParams &p);
 int64_t tile2d16_partial_rows(const ConvParams &p);     // one BatchNorm summary row per workgroup (image tile)
 int launch_tile2d16(const ConvParams &p, hipStream_t st);

@@ -280,6 +280,12 @@ extern "C" size_t eprecon_conv_bn_partial_bytes(int64_t n_out, int cout)
     return (size_t)ep::ceil_div(n_out > 0 ? n_out : 1, (int64_t)128) * 3 * (size_t)(cout > 0 ? cout : 1) * sizeof(float);
 }
 
+// bytes addressable from x: n_in rows of ld_x floats, the last one C_in floats rounded up to the 16-byte gathers
+static int64_t conv_x_bytes(const ConvParams &p, int64_t n_in)
+{
+    return n_in > 0 ? ((n_in - 1) * (int64_t)p.ld_x + ((p.Cin + 3) & ~3)) * 4 : 0;
+}
+
 static int conv_check_and_run(ConvParams &p, int64_t n_in, int64_t n_out, void *stream)
 {
     if (!p.x || !p.w || !p.out || n_in < 0 || n_out < 0 || p.K <= 0 || p.K > 64 || p.Cin <= 0 || p.Cout <= 0 ||
@@ -292,7 +298,7 @@ static int conv_check_and_run(ConvParams &p, int64_t n_in, int64_t n_out, void *
     if (p.Cout > 4096 || n_out > 0x7fffffff) return EPRECON_ERR_UNSUPPORTED;
     if (n_out == 0) return EPRECON_OK;
     p.n_out = (int)n_out;
-    p.x_bytes = n_in > 0 ? ((n_in - 1) * (int64_t)p.ld_x + ((p.Cin + 3) & ~3)) * 4 : 0;
+    p.x_bytes = conv_x_bytes(p, n_in);
     return conv_dispatch(p, (hipStream_t)stream);
 }
 
@@ -317,6 +323,19 @@ static void params_from_desc(ConvParams &p, const eprecon_conv_desc *d)
     p.in_acc = d->in_acc; p.in_acc_ld = d->in_acc_ld; p.in_acc_c0 = d->in_acc_c0; p.in_eps = d->in_eps;
 }
 
+// What the descriptor's entry points ask the family rules with: the described launch with n_out / x_bytes set the way
+// conv_check_and_run sets them.  false: no descriptor, or a row count that launches nothing (0, or more than 2^31 - 1 rows);
+// p.n_out is 0 then.
+static bool query_params(ConvParams &p, const eprecon_conv_desc *d)
+{
+    if (!d) return false;
+    params_from_desc(p, d);
+    const bool rows = d->n_out > 0 && d->n_out <= 0x7fffffff;
+    p.n_out = rows ? (int)d->n_out : 0;
+    p.x_bytes = conv_x_bytes(p, d->n_in);
+    return rows;
+}
+
 extern "C" int eprecon_batchnorm_acc_affine_async(const long long *acc, int acc_ld, int acc_c0, int channels, float eps,
                                                   float *scale_out, float *shift_out, void *stream);
 
@@ -333,11 +352,16 @@ extern "C" size_t eprecon_bn_acc_words(int ld)
 
 extern "C" int eprecon_conv_desc_takes_bn_acc(const eprecon_conv_desc *d)
 {
-    if (!d || d->n_out <= 0) return 0;
     ConvParams p = {};
-    params_from_desc(p, d);
-    p.n_out = (int)d->n_out;
-    return !p.ln && !p.accumulate && bn_acc_family(p) ? 1 : 0;
+    return query_params(p, d) && !p.ln && !p.accumulate && bn_acc_family(p) ? 1 : 0;
+}
+
+// which dense-grid kernel the described shape is for (0 none: the kernel map; 1 single column; 2 the 16-row kernel, which
+// then wants packed_weight16): what a caller asks before it packs weights and drops the kernel map.  Dereferences nothing.
+extern "C" int eprecon_conv_dense3d_kind(const eprecon_conv_desc *d)
+{
+    ConvParams p = {};
+    return query_params(p, d) ? conv3d_shape_kind(p) : kD3None;
 }
 
 extern "C" int64_t eprecon_conv_desc_partial_rows(const eprecon_conv_desc *d);
@@ -346,8 +370,7 @@ extern "C" int eprecon_conv_desc_async(const eprecon_conv_desc *d, void *stream)
 {
     if (!d) return EPRECON_ERR_ARG;
     ConvParams p = {};
-    params_from_desc(p, d);
-    p.n_out = (int)(d->n_out > 0 && d->n_out <= 0x7fffffff ? d->n_out : 0);
+    query_params(p, d);     // (an empty or oversized launch is conv_check_and_run's to answer)
     if (p.bn_partial) {     // row stride of the channel-major summaries: at least the rows this launch writes
         const int64_t rows = eprecon_conv_desc_partial_rows(d);
         if (p.bn_ld == 0) p.bn_ld = (int)(rows > 0 ? rows : 1);
@@ -375,23 +398,16 @@ extern "C" int eprecon_conv_desc_async(const eprecon_conv_desc *d, void *stream)
 
 extern "C" size_t eprecon_conv_desc_workspace_bytes(const eprecon_conv_desc *d)
 {
-    if (!d || d->n_out <= 0 || d->n_out > 0x7fffffff) return 0;
     ConvParams p = {};
-    params_from_desc(p, d);
-    p.n_out = (int)d->n_out;
-    return wide_shape_ok(p) ? wide_workspace_bytes(p) : 0;
+    return query_params(p, d) && wide_shape_ok(p) ? wide_workspace_bytes(p) : 0;
 }
 
 // rows of bn_partial the launch described by `d` writes (= the nblk to hand to
 // eprecon_batchnorm_finalize_affine_async): the workgroups of the family select_conv gives the launch to
 extern "C" int64_t eprecon_conv_desc_partial_rows(const eprecon_conv_desc *d)
 {
-    if (!d || d->n_out <= 0) return 0;
     ConvParams p = {};
-    params_from_desc(p, d);
-    p.n_out = (int)d->n_out;
-    p.x_bytes = d->n_in > 0 ? ((d->n_in - 1) * (int64_t)p.ld_x + ((p.Cin + 3) & ~3)) * 4 : 0;
-    return select_conv(p).partial_rows;
+    return query_params(p, d) ? select_conv(p).partial_rows : 0;
 }
 
 // out = [ReLU]( sum_k x[nbr[k]] @ W[k] + bias [+ out] ) [+ residual]; optionally the per-workgroup

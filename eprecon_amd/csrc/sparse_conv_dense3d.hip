@@ -397,9 +397,10 @@ inline int d3_level()
     return e ? atoi(e) : 2;
 }
 
-// which dense-grid kernel takes this layer: level 1 the single-column kernel, level 2 also the 16-row MFMA kernel
+// which dense-grid kernel the SHAPE of this layer is for (everything but the weight packing: what the caller asks through
+// eprecon_conv_dense3d_kind before it packs): level 1 the single-column kernel, level 2 also the 16-row MFMA kernel
 // (C_out <= 32, C_in a multiple of 16); every other shape runs on the kernel map
-int conv3d_kind(const ConvParams &p)
+int conv3d_shape_kind(const ConvParams &p)
 {
     const int level = d3_level();
     if (level <= 0 || !p.vox_rank || p.K != 27 || p.gx <= 0 || p.gy <= 0 || p.gz <= 0) return kD3None;
@@ -408,11 +409,17 @@ int conv3d_kind(const ConvParams &p)
         return kD3None;
     if (p.Cout == 1 && !p.ln) return kD3Narrow;
     if (level < 2 || p.accumulate) return kD3None;
-    // (the caller packs the weights for the kernel ITS mirror of this rule picks — eprecon_amd/sparse.py DenseMap.kind —,
-    // so a missing packing means "not this kernel", never an error)
-    if (p.Cout <= 32 && p.Cin % 16 == 0 && !(p.ln && p.bn_partial) && p.wq16 && (reinterpret_cast<uintptr_t>(p.wq16) & 15) == 0)
-        return kD3Tile16;
+    if (p.Cout <= 32 && p.Cin % 16 == 0 && !(p.ln && p.bn_partial)) return kD3Tile16;
     return kD3None;
+}
+
+// ... and which one takes the launch: the 16-row kernel only with its packing (a missing one means "not this kernel", never
+// an error)
+int conv3d_kind(const ConvParams &p)
+{
+    const int kind = conv3d_shape_kind(p);
+    if (kind == kD3Tile16 && (!p.wq16 || (reinterpret_cast<uintptr_t>(p.wq16) & 15) != 0)) return kD3None;
+    return kind;
 }
 
 int launch_conv3d_16(const ConvParams &p, hipStream_t st)

@@ -2,7 +2,7 @@
 // ops/torchsparse_utils.py:40-105) issued from ONE library call: 27 convolutions, their train-mode BatchNorms, 3 scatter-means
 // and 3 trilinear devoxelisations — ~115 launches that eprecon_amd/modules.py otherwise issues one by one from Python at ~15 us
 // of host time each (here ~3 us).  Nothing new is computed: the call fills the same descriptors with the same rules
-// (eprecon_amd/sparse.py: conv_stats / _resolve_map, batchnorm_apply_partials, bn_affine) and calls the same entry points in the
+// (eprecon_amd/sparse.py: conv_stats / conv_packings, batchnorm_apply_partials, bn_affine) and calls the same entry points in the
 // same order, so the results are bit-identical to the Python-issued pass (tests/test_spvcnn_gpu.py, tests/test_switches_gpu.py).
 // What it buys (profiles/r05/cfg4_switches_ab_all.txt): the host runs ~1 ms per pass further ahead of the GPU; a
 // fragment that is bound by its kernels (12.8 of ~13.4 ms busy) does not get shorter by it — interleaved A/Bs put the call between
@@ -12,12 +12,12 @@
 #include <vector>
 
 #include "common.hpp"
+#include "conv_common.hpp"
 
 namespace {
 using namespace ep;
-
-constexpr int kDirectMaxCout = 64;        // eprecon_amd/sparse.py DIRECT_MAX_COUT
-constexpr int64_t kK1DirectMinRows = 20000;  // eprecon_amd/sparse.py K1_DIRECT_MIN_ROWS
+using epconv::kDirectMaxCout;
+using epconv::kK1DirectMinRows;
 
 // conv / BatchNorm slots of the descriptor (eprecon_spvcnn_forward_desc.conv[] / .bn[]): the order of the launches
 enum Slot {
@@ -131,7 +131,8 @@ struct Pass {
         c.weight = w.weight; c.cin = w.cin; c.cout = w.cout;
         c.out = out.p; c.ld_out = out.ld;
         c.in_scale = in_scale; c.in_shift = in_shift; c.in_relu = in_scale ? 1 : 0;
-        // sparse._resolve_map: which operand-order packings ride along (the library picks the kernel)
+        // sparse.conv_packings, on the row count of this pass: which operand-order packings ride along (the library picks the
+        // kernel)
         if (!nbr && w.kvol == 1 && w.cout <= kDirectMaxCout && x.n >= kK1DirectMinRows) c.packed_weight16 = w.packed_weight16;
         if (nbr && w.kvol == 27 && w.cout <= kDirectMaxCout) c.packed_weight16 = w.packed_weight16;
         if (nbr && w.kvol == 27) c.packed_weight = w.packed_weight;
@@ -139,7 +140,7 @@ struct Pass {
             step(EPRECON_ERR_ARG);
             return nullptr;
         }
-        const size_t need = eprecon_conv_desc_workspace_bytes(&c);      // sparse._attach_workspace
+        const size_t need = eprecon_conv_desc_workspace_bytes(&c);      // sparse.ConvCall: the workspace query
         if (need) {
             c.workspace = alloc(need);
             c.workspace_bytes = need;

@@ -200,47 +200,19 @@ def conv_bn_act(conv, bn, x, grid, out=None, aff=None, relu=True, pre_relu=False
 def conv_bn_launch(w, bias, gamma, beta, eps, k, x, grid, out=None, aff=None, relu=True, pre_relu=False,
                    residual=None):
     lib = _lib.load()
-    kvol, cin, cout = w.shape
-    rows = x.rows
-    n = rows.shape[0]
-    dev = rows.device
-    assert rows.shape[1] == cin and rows.dtype == torch.float32 and rows.stride(1) == 1
-    nbr = grid.kernel_map(k)
-    if out is None:
-        out = torch.empty((n, cout), dtype=torch.float32, device=dev)
-    d = _lib.ConvDesc()
-    d.x, d.n_in, d.ld_x = rows.data_ptr(), n, rows.stride(0)
-    d.nbr, d.kvol, d.n_out = _dptr(nbr), kvol, n
-    d.weight, d.cin, d.cout = w.data_ptr(), cin, cout
-    d.bias = _dptr(bias)
-    if residual is not None:
-        assert residual.rows.shape == (n, cout)
-        d.residual, d.ld_res = residual.rows.data_ptr(), residual.rows.stride(0)
-        r_scale, r_shift = residual.affine()
-        d.res_scale, d.res_shift, d.res_relu = _dptr(r_scale), _dptr(r_shift), int(residual.relu)
-    d.out, d.ld_out = out.data_ptr(), out.stride(0)
-    d.relu, d.accumulate = int(pre_relu), 0
-    if x.acc is not None and x.scale is None:     # the input's BatchNorm is finished by this launch's prologue
-        assert x.acc.c == cin
-        d.in_acc, d.in_acc_ld, d.in_acc_c0, d.in_eps = x.acc.block.data_ptr(), x.acc.ld, x.acc.c0, float(x.eps)
-    else:
-        d.in_scale, d.in_shift = _dptr(x.scale), _dptr(x.shift)
-    d.in_relu = int(x.relu)
-    if k == 3:
-        d.img_h, d.img_w, d.img_maps = grid.height, grid.width, grid.maps  # narrow layers: image-tile kernel
-        if n < DIRECT_2D_MIN_ROWS:
-            pq = SP.packed_weight(w)                 # short pixel lists (the 10,800-pixel level): B operands of the split-K kernel
-            d.packed_weight = pq.data_ptr()
-            if n < SHORT_2D_MAX_ROWS and cout <= SHORT_2D_MAX_COUT:   # ... and of the short-list image-tile kernel (preferred)
-                d.packed_weight16 = SP.packed_weight16(w).data_ptr()
-        if cout <= SP.DIRECT_MAX_COUT and n >= DIRECT_2D_MIN_ROWS:
-            pw = SP.packed_weight16(w)               # long pixel lists: the direct gather kernel on the pixel map
-            d.packed_weight16 = pw.data_ptr()
-    elif k == 1 and cout <= SP.DIRECT_MAX_COUT and n >= K1_DIRECT_2D_MIN_ROWS:
-        # point-wise layers on long pixel lists: the direct kernel as a streaming product (sparse.K1_DIRECT_MIN_ROWS' rule; the
-        # slab kernel took 144 -> 32 on 43,200 pixels in 23 us, 160 -> 40 in 34, 96 -> 24 on 172,800 in 37: 14 / 19 / 30 on this one)
-        pw = SP.packed_weight16(w)
-        d.packed_weight16 = pw.data_ptr()
+    cout = w.shape[2]
+    dev = x.rows.device
+    # 3x3 layers name their image (the image-tile kernels need no kernel map) and hand packings over by the pixel-list rules at the
+    # head of this file; point-wise layers by K1_DIRECT_2D_MIN_ROWS (the slab kernel took 144 -> 32 on 43,200 pixels in 23 us,
+    # 160 -> 40 in 34, 96 -> 24 on 172,800 in 37: 14 / 19 / 30 on the direct kernel as a streaming product)
+    acc_in = x.acc is not None and x.scale is None      # the input's BatchNorm is finished by this launch's prologue
+    out, _, d, _keep = SP.conv_call(      # (_keep: the temporaries of the launch, alive until it is queued below)
+        x.rows, w, grid.kernel_map(k), bias, out, relu=pre_relu, residual=None if residual is None else residual.rows,
+        res_affine=None if residual is None else (*residual.affine(), residual.relu),
+        in_affine=(x.scale, x.shift, x.relu) if x.scale is not None or x.relu else None,
+        in_acc=(x.acc, x.eps, x.relu) if acc_in else None,
+        image=(grid.height, grid.width, grid.maps) if k == 3 else None, launch=False, k1_min_rows=K1_DIRECT_2D_MIN_ROWS,
+        image_limits=(DIRECT_2D_MIN_ROWS, SHORT_2D_MAX_ROWS, SHORT_2D_MAX_COUT) if k == 3 else None)
     if _ARENA is not None and (aff is None or isinstance(aff, AccSlice)) and lib.eprecon_conv_desc_takes_bn_acc(ctypes.byref(d)):
         # the launch sums into an accumulator block; whoever consumes the result finishes the BatchNorm: no finalize launch
         acc = aff if aff is not None else AccSlice.new(cout)
@@ -254,9 +226,8 @@ def conv_bn_launch(w, bias, gamma, beta, eps, k, x, grid, out=None, aff=None, re
         aff = (a[0], a[1])
     assert not isinstance(aff, AccSlice), "an accumulator slice was handed to a launch that cannot produce into it"
     # the summaries are per workgroup: 128-row blocks (gather forms) or image tiles (tile kernel)
-    partial = SP.bn_summaries(lib.eprecon_conv_desc_partial_rows(ctypes.byref(d)), cout, dev)
-    nblk, ld = SP.summary_layout(partial)
-    d.bn_partial, d.bn_ld = partial.data_ptr(), ld
+    partial = SP.attach_summaries(d, dev)
+    nblk, ld = partial.shape[0], d.bn_ld
     _lib.check(lib.eprecon_conv_desc_async(ctypes.byref(d), _lib.current_stream()), "eprecon_conv_desc_async")
     _lib.check(lib.eprecon_batchnorm_finalize_affine_async(
         partial.data_ptr(), nblk, ld, cout, _dptr(gamma), _dptr(beta), float(eps),

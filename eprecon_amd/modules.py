@@ -748,11 +748,13 @@ class SPVCNN(nn.Module):
                 e = d.conv[slot]
                 e.weight, e.kvol, e.cin, e.cout = wc.data_ptr(), kvol, ci, co
                 keep.append(wc)
-                if kvol == 27:
+                # (every packing a launch of the slot may be handed: the pass applies the row-count part of the rule itself)
+                pack, pack16 = SP.conv_packings(kvol, co, 0, mapped=kvol != 1, k1_min_rows=0)
+                if pack:
                     pw = SP.packed_weight(w)
                     e.packed_weight = pw.data_ptr()
                     keep.append(pw)
-                if kvol in (27, 1) and co <= SP.DIRECT_MAX_COUT:
+                if pack16:
                     pw16 = SP.packed_weight16(w3, owner=w)
                     e.packed_weight16 = pw16.data_ptr()
                     keep.append(pw16)

@@ -6,23 +6,23 @@ Coordinates are int32[N,4] rows (batch, x, y, z) everywhere in this package; wra
 torchsparse's xyzb order convert at their boundary.
 """
 import ctypes
+import os
 
 import torch
 
 from . import _lib
 
 
-import os
-
 def _dense3d_level():
-    """EPRECON_CONV_DENSE3D: 0 off, 1 the single-column (C_out == 1) kernel only, 2 (default) also the 16-row MFMA tile kernel
-    (C_out <= 32, C_in % 16 == 0); csrc/sparse_conv_dense3d.hip, conv3d_kind"""
+    """EPRECON_CONV_DENSE3D: 0 the dense-grid form is off (all VoxelSet.conv_map asks here; which kernel a layer gets at levels
+    1 and 2 is the library's answer: DenseMap.kind)"""
     return int(os.environ.get("EPRECON_CONV_DENSE3D", "2"))
 
 
 def _ld(t):
-    assert t.dim() == 2 and t.stride(1) == 1, "row-major 2-D tensor expected"
-    return t.stride(0)
+    ld, unit = t.stride()       # (two strides: a 2-D tensor)
+    assert unit == 1, "row-major 2-D tensor expected"
+    return ld
 
 
 class HashGrid:
@@ -168,19 +168,29 @@ class DenseMap:
         """blocking: number of voxels that were not on the grid (0 for a valid set)"""
         return int(self.rank[-1].item())
 
+    def describe(self, desc, stats=False):
+        """Ask the library which dense-grid kernel it has for the 3x3x3 launch `desc` describes on this grid (x, the channel
+        counts, the pending input BatchNorm, ln and accumulate are set; stats: it will write BatchNorm summaries):
+        eprecon_conv_dense3d_kind, the shape rule of csrc/sparse_conv_dense3d.hip -> 0 none, 1 single-column kernel, 2 16-row
+        MFMA kernel (which wants packed_weight16).  The grid stays in `desc` unless the answer is 0."""
+        desc.vox_rank = self.rank.data_ptr()
+        desc.grid_x, desc.grid_y, desc.grid_z = self.dims
+        # (the rule asks WHETHER summaries are written; their buffer is sized once the kernel is known: any address will do)
+        desc.bn_partial = 1 if stats else None
+        kind = int(_lib.load().eprecon_conv_dense3d_kind(ctypes.byref(desc)))
+        desc.bn_partial = None
+        if not kind:
+            desc.vox_rank, desc.grid_x, desc.grid_y, desc.grid_z = None, 0, 0, 0
+        return kind
+
     def kind(self, x, cin, cout, accumulate=False, ln=False, stats=False):
-        """mirror of the library's rule (conv3d_kind, csrc/sparse_conv_dense3d.hip): 0 none (kernel map), 1 single-column kernel,
-        2 16-row MFMA kernel"""
-        level = _dense3d_level()
-        if level <= 0 or cin % 4 or cin > 64 or x.stride(0) % 4 or x.data_ptr() % 16:
-            return 0
-        if cout == 1 and not ln:
-            return 1
-        if level < 2 or accumulate:
-            return 0
-        if cout <= 32 and cin % 16 == 0 and not (ln and stats):
-            return 2
-        return 0
+        """the library's answer for a layer of this shape on x: 0 none (kernel map), 1 single-column kernel, 2 16-row MFMA
+        kernel"""
+        d = _lib.ConvDesc()
+        d.x, d.ld_x, d.n_in, d.n_out = x.data_ptr(), x.stride(0), self.vset.n, self.vset.n
+        d.kvol, d.cin, d.cout = 27, cin, cout
+        d.accumulate, d.ln = int(accumulate), int(ln)
+        return self.describe(d, stats)
 
     def takes(self, x, cin, cout, accumulate=False, ln=False, stats=False):
         return self.kind(x, cin, cout, accumulate, ln, stats) != 0
@@ -357,43 +367,30 @@ def clear_packed_weights(module):
 K1_DIRECT_MIN_ROWS = 20000
 
 
-def _resolve_map(nbr, x, weight, desc, accumulate=False, ln=False, stats=False, owner=None):
-    """nbr: None (identity), an int32[K, N] kernel map, or a DenseMap -> fills the map fields of `desc`; returns the
-    objects that must stay alive until the launch is queued.  owner: the caller's weight object (packings are cached on it)"""
-    if isinstance(nbr, DenseMap):
-        kvol, cin, cout = weight.shape
-        kind = nbr.kind(x, cin, cout, accumulate, ln, stats) if kvol == 27 else 0
-        if kind:
-            desc.vox_rank = nbr.rank.data_ptr()
-            desc.grid_x, desc.grid_y, desc.grid_z = nbr.dims
-            keep = [nbr.rank]
-            if kind == 2:
-                pw = packed_weight16(weight)
-                desc.packed_weight16 = pw.data_ptr()
-                keep.append(pw)
-            desc.nbr = None
-            return keep
-        nbr = nbr.vset.kernel_map(3)
-    desc.nbr = None if nbr is None else nbr.data_ptr()
-    keep = [nbr]
-    if nbr is None and weight.shape[0] == 1 and weight.shape[2] <= DIRECT_MAX_COUT and not accumulate and x.is_cuda \
-            and x.shape[0] >= K1_DIRECT_MIN_ROWS:
-        pw = packed_weight16(weight, owner)
-        desc.packed_weight16 = pw.data_ptr()
-        keep.append(pw)
-    if nbr is not None and weight.shape[0] == 27 and weight.shape[2] <= DIRECT_MAX_COUT \
-            and not accumulate and x.is_cuda:
-        # long lists: the direct gather kernel takes its B operands pre-packed (csrc/sparse_conv_direct_kernels.hpp,
-        # spconv_direct16_kernel); which kernel runs is the library's choice, the packing only makes the direct one possible
-        pw = packed_weight16(weight)
-        desc.packed_weight16 = pw.data_ptr()
-        keep.append(pw)
-    if nbr is not None and weight.shape[0] == 27 and not accumulate and x.is_cuda:
-        # short lists: the split-K kernel reads its B operands straight from the 32x32x2 operand-order packing
-        pw = packed_weight(weight)
-        desc.packed_weight = pw.data_ptr()
-        keep.append(pw)
-    return keep
+def conv_packings(kvol, cout, rows, mapped, accumulate=False, dense_kind=0, k1_min_rows=None, image_limits=None):
+    """THE hand-over rule: which operand-order copies of its weights ride along with a described launch
+    -> (packed_weight, packed_weight16).  Which kernel runs is the library's choice (select_conv, csrc/sparse_conv.hip); a
+    packing only makes the kernels that read it possible, and they decline without it.
+    rows: output rows; mapped: the launch has a kernel map (False: identity map); dense_kind: DenseMap.describe's answer for a
+    launch that stays on the dense grid; k1_min_rows: the caller's threshold for point-wise layers in place of
+    K1_DIRECT_MIN_ROWS (dense2d: K1_DIRECT_2D_MIN_ROWS; 0, "any length", where a descriptor is built before the row count exists:
+    SPVCNN._native_desc, whose launches csrc/spvcnn_forward.hip then holds to kK1DirectMinRows); image_limits: dense2d's
+    (DIRECT_2D_MIN_ROWS, SHORT_2D_MAX_ROWS, SHORT_2D_MAX_COUT) for a 3x3 image layer"""
+    if dense_kind:                 # the 16-row tile kernel reads the 16x16x4 order, the single-column kernel the plain weights
+        return False, dense_kind == 2
+    if accumulate:
+        return False, False
+    direct = cout <= DIRECT_MAX_COUT
+    if kvol == 1 and not mapped:   # point-wise layers on long lists: the direct kernel as a streaming product
+        return False, direct and rows >= (K1_DIRECT_MIN_ROWS if k1_min_rows is None else k1_min_rows)
+    if kvol == 27 and mapped:      # short lists: split-K (and the cross-workgroup kernel) on the 32x32x2 order; long lists: the
+        return True, direct        # direct gather kernel on the 16x16x4 order
+    if kvol == 9 and image_limits is not None:
+        direct_min_rows, short_max_rows, short_max_cout = image_limits
+        if rows < direct_min_rows:     # short pixel lists: split-K, and below short_max_rows the short-list image-tile kernel
+            return True, rows < short_max_rows and cout <= short_max_cout
+        return False, direct           # long pixel lists: the direct gather kernel on the pixel map / the 16-row image-tile kernel
+    return False, False
 
 
 class VoxelSet:
@@ -471,41 +468,10 @@ class VoxelSet:
         return self._down
 
 
-def _attach_workspace(desc, device):
-    """scratch for the kernels that reduce partial sums across workgroups (medium lists with wide channels): the library says
-    how much the described launch wants (0 for every other shape); returns the buffer to keep alive until the launch is queued"""
-    need = int(_lib.load().eprecon_conv_desc_workspace_bytes(ctypes.byref(desc)))
-    if not need:
-        return None
-    ws = _lib.workspace(need, device)
-    desc.workspace, desc.workspace_bytes = ws.data_ptr(), ws.numel()
-    return ws
-
-
 def sparse_conv(x, weight, nbr=None, bias=None, out=None, relu=False, accumulate=False):
     """out[i] (op)= bias + sum_k x[nbr[k][i]] @ weight[k].  weight f32[K, Cin, Cout] (or [Cin, Cout]
     with nbr None: a per-voxel linear layer).  x / out may be column slices of wider buffers."""
-    lib = _lib.load()
-    w_owner = weight
-    if weight.dim() == 2:
-        weight = weight.unsqueeze(0)
-    kvol, cin, cout = weight.shape
-    weight = weight.contiguous()
-    n_out = x.shape[0] if nbr is None else nbr.shape[1]
-    assert x.shape[1] == cin and x.dtype == torch.float32
-    if isinstance(nbr, DenseMap) or (kvol == 27 and nbr is not None and x.is_cuda) or \
-            (kvol == 1 and nbr is None and x.is_cuda and cout <= DIRECT_MAX_COUT and not accumulate and n_out >= K1_DIRECT_MIN_ROWS):
-        return sparse_conv_fused(x, w_owner, nbr, bias, out, relu, None, accumulate)[0]
-    if nbr is not None:
-        assert nbr.dtype == torch.int32 and nbr.shape[0] == kvol and nbr.is_contiguous()
-    if out is None:
-        out = torch.empty((n_out, cout), dtype=torch.float32, device=x.device)
-    assert out.shape == (n_out, cout)
-    _lib.check(lib.eprecon_sparse_conv_async(_lib.ptr(x), x.shape[0], _ld(x), _lib.ptr(nbr), kvol, n_out,
-                                             _lib.ptr(weight), cin, cout, _lib.ptr(bias), _lib.ptr(out),
-                                             _ld(out), int(relu), int(accumulate), _lib.current_stream()),
-               "eprecon_sparse_conv_async")
-    return out
+    return conv_call(x, weight, nbr, bias, out, relu, accumulate, positional=True)[0]     # = sparse_conv_fused(...)[0]
 
 
 def bn_summaries(rows, cout, device):
@@ -523,93 +489,132 @@ def summary_layout(partial):
     return nblk, s2
 
 
+def attach_summaries(desc, device):
+    """size the BatchNorm summaries for the kernel the library gives the described launch to (the workgroups differ from family
+    to family) and attach them -> the [rows, 3, cout] view"""
+    rows = max(int(_lib.load().eprecon_conv_desc_partial_rows(ctypes.byref(desc))), 1)
+    partial = bn_summaries(rows, desc.cout, device)
+    desc.bn_partial, desc.bn_ld = partial.data_ptr(), rows      # (bn_summaries' layout: the row stride is the row count)
+    return partial
+
+
+def conv_call(x, weight, nbr=None, bias=None, out=None, relu=False, accumulate=False, residual=None, res_affine=None,
+              in_affine=None, in_acc=None, ln=None, image=None, stats=False, positional=False, launch=True,
+              k1_min_rows=None, image_limits=None):
+    """THE host path of a convolution launch, for every wrapper: operands normalised and checked, `out` allocated, the
+    eprecon_conv_desc filled, the map resolved, the packings of conv_packings attached, the workspace and (stats) the BatchNorm
+    summaries the library asks for, the launch -> (out, summaries or None, descriptor, temporaries).
+    weight f32[K, Cin, Cout], or [Cin, Cout] (K = 1): operand-order packings are cached on the object given here; nbr: None
+    (identity map), an int32[K, N] kernel map or a DenseMap; res_affine / in_affine = (scale, shift, relu): the pending BatchNorm
+    of the residual / the input, applied on load; in_acc = (accumulator slice, eps, relu): the input's BatchNorm still in its
+    accumulator block; ln = (gamma, beta, eps, post_relu): row-wise LayerNorm epilogue; image = (height, width, maps) of a 3x3
+    image layer; k1_min_rows / image_limits: see conv_packings.
+    positional: the caller has no fusion beyond the positional eprecon_sparse_conv_fused_async and takes it where the routing
+    below says so (no descriptor is returned then).  launch=False: the caller finishes the descriptor (dense2d's BatchNorm
+    tail) and queues it, holding the temporaries until then."""
+    lib = _lib.load()
+    owner = weight
+    if weight.dim() == 2:
+        weight = weight.unsqueeze(0)
+    kvol, cin, cout = weight.shape
+    weight = weight.contiguous()
+    dense = isinstance(nbr, DenseMap)
+    n_in, c_x = x.shape
+    n_out = n_in
+    if nbr is not None:
+        k_map, n_out = nbr.shape
+        assert dense or (nbr.dtype == torch.int32 and k_map == kvol and nbr.is_contiguous())
+    assert c_x == cin and x.dtype == torch.float32
+    if out is None:
+        out = torch.empty((n_out, cout), dtype=torch.float32, device=x.device)
+    assert out.shape == (n_out, cout)
+    (ld_x, unit_x), (ld_out, unit_out) = x.stride(), out.stride()
+    assert unit_x == 1 and unit_out == 1, "row-major 2-D tensors expected"
+    if residual is not None:
+        assert residual.shape == (n_out, cout) and residual.dtype == torch.float32
+    pack, pack16 = conv_packings(kvol, cout, n_out, nbr is not None, accumulate, 0, k1_min_rows, image_limits)
+    # Routing of sparse_conv_fused: a DenseMap, a 3x3x3 layer on a kernel map and every launch with a packing to hand over
+    # (point-wise layers on long lists) go through the descriptor; everything else takes the positional entry point, whose
+    # summaries are per 128 rows (the kernels with other workgroups decline it)
+    if positional and not (dense or (x.is_cuda and ((kvol == 27 and nbr is not None) or pack or pack16))):
+        partial = bn_summaries((n_out + 127) // 128, cout, x.device) if stats else None
+        _lib.check(lib.eprecon_sparse_conv_fused_async(
+            x.data_ptr(), n_in, ld_x, _lib.ptr(nbr), kvol, n_out, _lib.ptr(weight), cin, cout, _lib.ptr(bias),
+            _lib.ptr(residual), _ld(residual) if residual is not None else 0, out.data_ptr(), ld_out, int(relu),
+            int(accumulate), _lib.ptr(partial), _lib.current_stream()), "eprecon_sparse_conv_fused_async")
+        return out, partial, None, None
+    d = _lib.ConvDesc()
+    d.x, d.n_in, d.ld_x = x.data_ptr(), n_in, ld_x
+    d.kvol, d.n_out = kvol, n_out
+    d.weight, d.cin, d.cout = weight.data_ptr(), cin, cout
+    if bias is not None:
+        d.bias = bias.data_ptr()
+    if residual is not None:
+        d.residual, d.ld_res = residual.data_ptr(), _ld(residual)
+        if res_affine is not None:
+            d.res_scale, d.res_shift, d.res_relu = _lib.ptr(res_affine[0]), _lib.ptr(res_affine[1]), int(res_affine[2])
+    d.out, d.ld_out = out.data_ptr(), ld_out
+    if relu:
+        d.relu = 1
+    if accumulate:
+        d.accumulate = 1
+    if in_acc is not None:
+        acc, eps, in_relu = in_acc
+        assert acc.c == cin
+        d.in_acc, d.in_acc_ld, d.in_acc_c0, d.in_eps, d.in_relu = acc.block.data_ptr(), acc.ld, acc.c0, float(eps), int(in_relu)
+    elif in_affine is not None:
+        d.in_scale, d.in_shift, d.in_relu = _lib.ptr(in_affine[0]), _lib.ptr(in_affine[1]), int(in_affine[2])
+    if ln is not None:
+        assert cout <= 128
+        d.ln, d.ln_gamma, d.ln_beta, d.ln_eps, d.ln_post_relu = 1, _lib.ptr(ln[0]), _lib.ptr(ln[1]), float(ln[2]), int(ln[3])
+    if image is not None:
+        d.img_h, d.img_w, d.img_maps = image
+    # the map: the dense grid where the library has a kernel for this shape on it, else the (set's) kernel map
+    if dense:
+        kind = nbr.describe(d, stats)
+        if kind:
+            nbr = nbr.rank
+            pack, pack16 = conv_packings(kvol, cout, n_out, True, accumulate, kind)
+        else:
+            nbr = nbr.vset.kernel_map(3)
+            d.nbr = nbr.data_ptr()
+    elif nbr is not None:
+        d.nbr = nbr.data_ptr()
+    keep = [weight, nbr]
+    if x.is_cuda:
+        if pack:
+            keep.append(packed_weight(weight))
+            d.packed_weight = keep[-1].data_ptr()
+        if pack16:
+            keep.append(packed_weight16(weight, owner))
+            d.packed_weight16 = keep[-1].data_ptr()
+    # scratch of the kernel pair that reduces partial sums across workgroups: the library says how much the described launch
+    # wants.  Asked only where the answer can be other than 0: wide_shape_ok (csrc/sparse_conv_wide.hip) needs K = 27, a
+    # kernel map, packed_weight, at least 96 input channels and no LayerNorm
+    if kvol == 27 and cin >= 96 and ln is None and d.packed_weight and d.nbr:
+        need = int(lib.eprecon_conv_desc_workspace_bytes(ctypes.byref(d)))
+        if need:
+            keep.append(_lib.workspace(need, x.device))
+            d.workspace, d.workspace_bytes = keep[-1].data_ptr(), need
+    partial = attach_summaries(d, x.device) if stats else None
+    if launch:
+        _lib.check(lib.eprecon_conv_desc_async(ctypes.byref(d), _lib.current_stream()), "eprecon_conv_desc_async")
+    return out, partial, d, keep
+
+
 def sparse_conv_fused(x, weight, nbr=None, bias=None, out=None, relu=False, residual=None, accumulate=False,
                       bn_partial=False):
     """sparse_conv with the fused epilogues: v = conv + bias [+ out]; [relu]; [+ residual]; and, with
     bn_partial, the per-workgroup BatchNorm summaries [ceil(n/128), 3, cout] of the stored values (a bn_summaries view).
     Returns (out, partial or None)."""
-    lib = _lib.load()
-    w_owner = weight
-    if weight.dim() == 2:
-        weight = weight.unsqueeze(0)
-    kvol, cin, cout = weight.shape
-    weight = weight.contiguous()
-    n_out = x.shape[0] if nbr is None else nbr.shape[1]
-    assert x.shape[1] == cin and x.dtype == torch.float32
-    k1_direct = kvol == 1 and nbr is None and x.is_cuda and cout <= DIRECT_MAX_COUT and not accumulate and n_out >= K1_DIRECT_MIN_ROWS
-    if isinstance(nbr, DenseMap) or (kvol == 27 and nbr is not None and x.is_cuda) or k1_direct:   # descriptor entry point
-        if nbr is not None and not isinstance(nbr, DenseMap):
-            assert nbr.dtype == torch.int32 and nbr.shape[0] == kvol and nbr.is_contiguous()
-        if out is None:
-            out = torch.empty((n_out, cout), dtype=torch.float32, device=x.device)
-        assert out.shape == (n_out, cout)
-        d = _lib.ConvDesc()
-        d.x, d.n_in, d.ld_x = x.data_ptr(), x.shape[0], _ld(x)
-        d.kvol, d.n_out = kvol, n_out
-        d.weight, d.cin, d.cout = weight.data_ptr(), cin, cout
-        d.bias = None if bias is None else bias.data_ptr()
-        if residual is not None:
-            assert residual.shape == (n_out, cout)
-            d.residual, d.ld_res = residual.data_ptr(), _ld(residual)
-        d.out, d.ld_out = out.data_ptr(), _ld(out)
-        d.relu, d.accumulate = int(relu), int(accumulate)
-        keep = _resolve_map(nbr, x, weight, d, accumulate=accumulate, stats=bn_partial, owner=w_owner)
-        keep.append(_attach_workspace(d, x.device))
-        partial = None
-        if bn_partial:
-            partial = bn_summaries(lib.eprecon_conv_desc_partial_rows(ctypes.byref(d)), cout, x.device)
-            d.bn_partial, d.bn_ld = partial.data_ptr(), summary_layout(partial)[1]
-        _lib.check(lib.eprecon_conv_desc_async(ctypes.byref(d), _lib.current_stream()), "eprecon_conv_desc_async")
-        del keep
-        return out, partial
-    if nbr is not None:
-        assert nbr.dtype == torch.int32 and nbr.shape[0] == kvol and nbr.is_contiguous()
-    if out is None:
-        out = torch.empty((n_out, cout), dtype=torch.float32, device=x.device)
-    assert out.shape == (n_out, cout)
-    partial = None
-    if bn_partial:
-        partial = bn_summaries((n_out + 127) // 128, cout, x.device)    # (the library's stride: ceil(n_out / 128))
-    if residual is not None:
-        assert residual.shape == (n_out, cout) and residual.dtype == torch.float32
-    _lib.check(lib.eprecon_sparse_conv_fused_async(
-        _lib.ptr(x), x.shape[0], _ld(x), _lib.ptr(nbr), kvol, n_out, _lib.ptr(weight), cin, cout, _lib.ptr(bias),
-        _lib.ptr(residual), _ld(residual) if residual is not None else 0, _lib.ptr(out), _ld(out), int(relu),
-        int(accumulate), _lib.ptr(partial), _lib.current_stream()), "eprecon_sparse_conv_fused_async")
-    return out, partial
+    return conv_call(x, weight, nbr, bias, out, relu, accumulate, residual, stats=bn_partial, positional=True)[:2]
 
 
 def sparse_conv_ln(x, weight, nbr, bias, ln_weight, ln_bias, ln_eps, out=None, relu=False, residual=None,
                    post_relu=False):
     """conv + bias [+ReLU] [+residual] -> row-wise LayerNorm [-> ReLU] in ONE launch (descriptor entry point):
     the spconv + LayerNorm blocks of the reference without a second pass over the tensor."""
-    lib = _lib.load()
-    w_owner = weight
-    if weight.dim() == 2:
-        weight = weight.unsqueeze(0)
-    kvol, cin, cout = weight.shape
-    weight = weight.contiguous()
-    n_out = x.shape[0] if nbr is None else nbr.shape[1]
-    assert x.shape[1] == cin and x.dtype == torch.float32 and cout <= 128
-    if out is None:
-        out = torch.empty((n_out, cout), dtype=torch.float32, device=x.device)
-    d = _lib.ConvDesc()
-    d.x, d.n_in, d.ld_x = x.data_ptr(), x.shape[0], _ld(x)
-    d.kvol, d.n_out = kvol, n_out
-    keep = _resolve_map(nbr, x, weight, d, ln=True, owner=w_owner)  # noqa: F841  (alive until the launch is queued)
-    d.weight, d.cin, d.cout = weight.data_ptr(), cin, cout
-    d.bias = None if bias is None else bias.data_ptr()
-    if residual is not None:
-        assert residual.shape == (n_out, cout)
-        d.residual, d.ld_res = residual.data_ptr(), _ld(residual)
-    d.out, d.ld_out = out.data_ptr(), _ld(out)
-    d.relu = int(relu)
-    d.ln = 1
-    d.ln_gamma = None if ln_weight is None else ln_weight.data_ptr()
-    d.ln_beta = None if ln_bias is None else ln_bias.data_ptr()
-    d.ln_eps, d.ln_post_relu = float(ln_eps), int(post_relu)
-    _lib.check(lib.eprecon_conv_desc_async(ctypes.byref(d), _lib.current_stream()), "eprecon_conv_desc_async")
-    return out
+    return conv_call(x, weight, nbr, bias, out, relu, False, residual, ln=(ln_weight, ln_bias, ln_eps, post_relu))[0]
 
 
 def affine_rows(x, scale, shift, residual=None, relu=False, out=None):
@@ -628,32 +633,9 @@ def affine_rows(x, scale, shift, residual=None, relu=False, out=None):
 def conv_stats(x, weight, nbr=None, in_affine=None, out=None, bias=None):
     """Convolution whose epilogue also writes the per-workgroup BatchNorm summaries of its output
     (descriptor entry point: any kernel of the family may be chosen).  in_affine = (scale, shift, relu): the
-    producer's pending BatchNorm applied while gathering.  Returns (out, partial)."""
-    lib = _lib.load()
-    w_owner = weight
-    if weight.dim() == 2:
-        weight = weight.unsqueeze(0)
-    kvol, cin, cout = weight.shape
-    weight = weight.contiguous()
-    n_out = x.shape[0] if nbr is None else nbr.shape[1]
-    assert x.shape[1] == cin and x.dtype == torch.float32
-    if out is None:
-        out = torch.empty((n_out, cout), dtype=torch.float32, device=x.device)
-    d = _lib.ConvDesc()
-    d.x, d.n_in, d.ld_x = x.data_ptr(), x.shape[0], _ld(x)
-    d.kvol, d.n_out = kvol, n_out
-    keep = _resolve_map(nbr, x, weight, d, stats=True, owner=w_owner)  # noqa: F841
-    d.weight, d.cin, d.cout = weight.data_ptr(), cin, cout
-    d.bias = None if bias is None else bias.data_ptr()
-    d.out, d.ld_out = out.data_ptr(), _ld(out)
-    if in_affine is not None:
-        d.in_scale, d.in_shift, d.in_relu = in_affine[0].data_ptr(), in_affine[1].data_ptr(), int(in_affine[2])
-    keep.append(_attach_workspace(d, x.device))
-    partial = bn_summaries(lib.eprecon_conv_desc_partial_rows(ctypes.byref(d)), cout, x.device)
-    d.bn_partial, d.bn_ld = partial.data_ptr(), summary_layout(partial)[1]
-    if n_out > 0:
-        _lib.check(lib.eprecon_conv_desc_async(ctypes.byref(d), _lib.current_stream()), "eprecon_conv_desc_async")
-    return out, partial
+    producer's pending BatchNorm applied while gathering.  Returns (out, partial).  An empty list launches nothing."""
+    rows = x.shape[0] if nbr is None else nbr.shape[1]
+    return conv_call(x, weight, nbr, bias, out, in_affine=in_affine, stats=True, launch=rows > 0)[:2]
 
 
 def bn_affine(partial, gamma, beta, eps):

@@ -395,6 +395,11 @@ int eprecon_conv_desc_async(const eprecon_conv_desc *desc, void *stream);
 size_t eprecon_conv_desc_workspace_bytes(const eprecon_conv_desc *desc);
 /* number of bn_partial rows the launch described by desc writes (nblk of the finalize call) */
 int64_t eprecon_conv_desc_partial_rows(const eprecon_conv_desc *desc);
+/* which dense-grid kernel the shape described by desc (vox_rank, grid_*, x, ld_x, cin, cout, in_scale / in_shift, ln,
+ * accumulate, bn_partial) is for: 0 none (the launch needs nbr), 1 the single-column kernel, 2 the 16-row tile kernel, which
+ * takes the launch when packed_weight16 is given.  Ask before packing weights or dropping the kernel map; host arithmetic,
+ * nothing is dereferenced.  EPRECON_CONV_DENSE3D is read per call. */
+int eprecon_conv_dense3d_kind(const eprecon_conv_desc *desc);
 /* producer-side summaries partial f32[3][channels][ld] (row r of channel c: partial[(q * channels + c) * ld + r], r < nblk <= ld)
  * -> the BatchNorm in affine form */
 int eprecon_batchnorm_finalize_affine_async(const float *partial, int64_t nblk, int64_t ld, int channels, const float *gamma,

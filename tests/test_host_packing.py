@@ -193,6 +193,65 @@ def test_summary_rows_and_workspace_per_convolution_family(monkeypatch):
     assert rows(_conv_desc(0, 27, 32, 32)) == 0 and ws(_conv_desc(0, 27, 96, 65, packed_weight=PACK)) == 0
 
 
+def test_dense_grid_kind_is_the_shape_rule_of_the_library(monkeypatch):
+    """eprecon_conv_dense3d_kind (what DenseMap asks before it packs weights or drops the kernel map) on both sides of every
+    clause of the rule, and its agreement with eprecon_conv_desc_partial_rows: kind 2 becomes the 16-row kernel's tile count
+    only with a packed_weight16"""
+    import ctypes
+    import os
+    from eprecon_amd import _lib
+    lib = _lib.load()
+    for name in [k for k in os.environ if k.startswith("EPRECON_CONV_")]:
+        monkeypatch.delenv(name)
+    monkeypatch.setenv("EPRECON_CONV_DIRECT", "0")       # (its summary rows depend on the device; no shape here is meant for it)
+    PACK16, RANK, AFF = 0x60000, 0x70000, 0x90000
+
+    def kind(cin=32, cout=16, n=700, kvol=27, **kw):
+        grid = dict(vox_rank=RANK, grid_x=9, grid_y=10, grid_z=11)
+        grid.update(kw)
+        return lib.eprecon_conv_dense3d_kind(ctypes.byref(_conv_desc(n, kvol, cin, cout, **grid)))
+
+    def rows(cin, cout, **kw):
+        d = _conv_desc(700, 27, cin, cout, vox_rank=RANK, grid_x=9, grid_y=10, grid_z=11, **kw)
+        return lib.eprecon_conv_desc_partial_rows(ctypes.byref(d))
+
+    assert lib.eprecon_conv_dense3d_kind(None) == 0
+    # C_in: a multiple of 4 up to 64 for either kernel, of 16 for the 16-row kernel
+    assert kind(cin=32, cout=1) == 1 and kind(cin=30, cout=1) == 0 and kind(cin=36, cout=1) == 1
+    assert kind(cin=64, cout=1) == 1 and kind(cin=68, cout=1) == 0
+    assert kind(cin=64) == 2 and kind(cin=68) == 0 and kind(cin=80) == 0
+    assert kind(cin=16) == 2 and kind(cin=36) == 0 and kind(cin=48) == 2
+    # C_out: one column (without LayerNorm), or up to 32 columns
+    assert kind(cout=1) == 1 and kind(cout=1, ln=1) == 2 and kind(cin=36, cout=1, ln=1) == 0
+    assert kind(cout=2) == 2 and kind(cout=32) == 2 and kind(cout=33) == 0
+    # LayerNorm with summaries and accumulate: not the 16-row kernel; the single-column kernel takes accumulate
+    assert kind(ln=1) == 2 and kind(bn_partial=0xa0000) == 2 and kind(ln=1, bn_partial=0xa0000) == 0
+    assert kind(accumulate=1) == 0 and kind(cout=1, accumulate=1) == 1
+    # alignment of x, its pitch and the pending BatchNorm's vectors
+    assert kind(ld_x=36) == 2 and kind(ld_x=34) == 0 and kind(cout=1, ld_x=34) == 0
+    assert kind(x=0x10004) == 0 and kind(cout=1, x=0x10004) == 0 and kind(x=0x10010) == 2
+    assert kind(in_scale=AFF, in_shift=AFF + 128) == 2 and kind(cout=1, in_scale=AFF, in_shift=AFF + 128) == 1
+    assert kind(in_scale=AFF + 4, in_shift=AFF + 128) == 0 and kind(in_scale=AFF, in_shift=AFF + 132) == 0
+    assert kind(cout=1, in_scale=AFF + 4, in_shift=AFF + 132) == 0
+    # no grid, an empty grid, another kernel volume, no rows
+    assert kind(vox_rank=None) == 0 and kind(grid_x=0) == 0 and kind(grid_y=0) == 0 and kind(grid_z=0) == 0
+    assert kind(kvol=8) == 0 and kind(kvol=1) == 0 and kind(n=0) == 0 and kind(n=1) == 2
+    # the packing is not part of the answer ...
+    assert kind(packed_weight16=PACK16) == 2 and kind(packed_weight16=PACK16 + 4) == 2
+    # ... it decides whether the launch gets the kernel: the 16-row kernel's 2 x 4 x 8 tiles, else the kernel-map family's rows
+    assert rows(32, 16, packed_weight16=PACK16) == 5 * 3 * 2
+    assert rows(32, 16) == _cdiv(700, 32) and rows(32, 16, packed_weight16=PACK16 + 4) == _cdiv(700, 32)
+    assert rows(32, 1) == 3 * 3 * 2                                                # the single-column kernel needs none
+    assert kind(cin=40, cout=32) == 0 and rows(40, 32, packed_weight16=PACK16) == _cdiv(700, 32)
+    # the levels of EPRECON_CONV_DENSE3D, read per call
+    monkeypatch.setenv("EPRECON_CONV_DENSE3D", "1")
+    assert kind(cout=1) == 1 and kind() == 0 and rows(32, 16, packed_weight16=PACK16) == _cdiv(700, 32)
+    monkeypatch.setenv("EPRECON_CONV_DENSE3D", "0")
+    assert kind(cout=1) == 0 and kind() == 0
+    monkeypatch.setenv("EPRECON_CONV_DENSE3D", "2")
+    assert kind(cout=1) == 1 and kind() == 2
+
+
 # lengths that straddle a scan tile (2,048) and the lengths at which the device scan changes its form (32,768; 4,096 tiles)
 _SCAN_EDGES = [0, 1, 2047, 2048, 2049, 32768, 32769, 8388608, 8388609]
 # the same products as three dimensions (2047 = 23 * 89, 2049 = 3 * 683, 32769 = 9 * 3641, 8388609 = 3 * 2796203)
