@@ -980,6 +980,35 @@ int eprecon_instance_vote_async(const int32_t *mapped_sem, const int32_t *rank, 
                                 int32_t *class_out, int32_t *count_out, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Panoptic scoring: the contingency table of predicted and ground-truth segments  (eprecon_amd/panoptic_score.py;
+ * the reference ships no scoring code: the rules are DESIGN.md 5b's)
+ *
+ * counts int64[(n_pred + 1) * (n_gt + 2)], row-major, cleared by the call: counts[p * (n_gt + 2) + g] = the sites of
+ * predicted segment p and ground-truth segment g.  A predicted rank lies in [-1, n_pred): -1 ("no prediction") is row
+ * n_pred.  A ground-truth rank lies in [-1, n_gt]: n_gt is the void column, -1 ("no ground truth here") is column
+ * n_gt + 1.  A site with a rank outside its range is skipped and status[0] (int32[2] on the device, cleared by the call)
+ * is set; status[1] is not used.  One integer add per distinct pair of a wave at the most (a wave carries the pair it met
+ * last from one round of sites to the next); a table of up to 8,192 entries is summed per workgroup in LDS first
+ * (EPRECON_PC_LDS=0: never).  Integer adds only: the table depends neither on the order nor on that path.
+ * n_pred, n_gt < 0: EPRECON_ERR_ARG; (n_pred + 1) * (n_gt + 2) > 2^22: EPRECON_ERR_UNSUPPORTED, before any launch.
+ *
+ * eprecon_pair_count_async: the sites are the n entries of two rank lists.
+ * eprecon_voxel_pair_count_async: the sites are the cells k of a lattice box (lattice_lo_host int32[3] its first cell,
+ *   which may be negative, lattice_dims_host int32[3] its extent, z fastest, fewer than 2^31 cells) on the PREDICTION's
+ *   grid.  World position per axis w = fl64(pred_origin_host[a]) + fl64(k) * pred_voxel.  The prediction's rank is
+ *   pred_rank[k] when k lies inside pred_dims_host, else -1.  The ground-truth cell is j = floor((w - fl64(gt_origin_host[a]))
+ *   / gt_voxel + 0.5), every operation in fp64 and rounded on its own; the ground-truth rank is gt_rank[j] when j lies inside
+ *   gt_dims_host and fabsf(gt_tsdf[j]) < gt_surface (compared in fp32), else -1.  Volumes are [X,Y,Z] with z fastest.
+ * ------------------------------------------------------------------------------------------ */
+int eprecon_pair_count_async(const int32_t *pred_rank, const int32_t *gt_rank, int64_t n, int n_pred, int n_gt, int64_t *counts,
+                             int32_t *status, void *stream);
+int eprecon_voxel_pair_count_async(const int32_t *pred_rank, const int32_t *gt_rank, const float *gt_tsdf,
+                                   const int32_t *pred_dims_host, const int32_t *gt_dims_host, const float *pred_origin_host,
+                                   const float *gt_origin_host, double pred_voxel, double gt_voxel, float gt_surface,
+                                   const int32_t *lattice_lo_host, const int32_t *lattice_dims_host, int n_pred, int n_gt,
+                                   int64_t *counts, int32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Nearest finest-level voxel  (K18)
  *
  * Replaces  torch.cdist + argmin(dim=1)                 models/mask3dformer.py:361-367
