@@ -56,6 +56,7 @@ SIGNATURES = {
     "eprecon_sparse_conv_fused_async": (_i, [_vp, _i64, _i, _vp, _i, _i64, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i,
                                              _vp, _vp]),
     "eprecon_conv_desc_async": (_i, [_vp, _vp]),
+    "eprecon_exclusive_scan_scratch_ints": (_sz, [_i64]),
     "eprecon_exclusive_scan_async": (_i, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "eprecon_conv_desc_partial_rows": (_i64, [_vp]),
     "eprecon_conv_dense3d_kind": (_i, [_vp]),

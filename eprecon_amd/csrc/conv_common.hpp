@@ -47,7 +47,8 @@ struct ConvParams {
     const float *wq16;  // ... in 16x16x4 operand order (pack_weights16_kernel): 16-row tile kernel, direct gather kernel
     int debug;  // always 0 in the library; timing probes build with it set: 1 no MFMA loop, 2 tile16: weights from the first offset, 4 no halo row loads
     int splitk_pipe;  // split-K kernel: 1 software-pipelined stages, 2 also B operands straight from the packed weights (wq)
-    void *ws;         // caller's scratch (eprecon_conv_desc.workspace): partial sums of the cross-workgroup split-K kernel
+    void *ws;         // caller's scratch (eprecon_conv_desc.workspace): partial sums of the cross-workgroup split-K kernel, or
+                      // the job counters of the persistent form (the two families share no shape)
     size_t ws_bytes;
     // BatchNorm form (c) (round 6): the producer adds its workgroups' per-channel sums to ORDER-INDEPENDENT
     // integer accumulators instead of (or beside) the per-workgroup summaries, and the consumer turns them into (scale, shift)
@@ -339,6 +340,7 @@ bool direct16_ok(const ConvParams &p);
 constexpr int kDirectRows = 128;          // output rows (and rows of a BatchNorm summary block) per workgroup
 int launch_direct16(const ConvParams &p, hipStream_t st);
 int direct16_partial_block_rows(const ConvParams &p);   // 128, or 32 when the persistent form takes the launch
+size_t direct16_workspace_bytes(const ConvParams &p);   // 0, or the persistent form's job counters
 
 // sparse_conv_tile2d.hip: the dense 2D 3x3 layers of the fusion stack on the 16-row image-tile kernel
 // long pixel lists only (the rule dense2d.DIRECT_2D_MIN_ROWS hands the wq16 packing over by); shorter lists: the short-list kernel

@@ -198,11 +198,12 @@ int ep::ensure_crop(EpMap *m, int dim)
         EP_HIP_CHECK(hipMalloc(&m->keep_rank, (size_t)cap * sizeof(int32_t)));
         m->row_cap = cap;
     }
-    const int64_t need = scan_scratch_ints(scan_n > rows ? scan_n : rows) + 8;
+    // two halves of scratch_cap int32, one per scan of a crop: the scans are queued back to back and a graph need not keep their order
+    const int64_t need = scan_scratch_ints(scan_n > rows ? scan_n : rows);
     if (need > m->scratch_cap) {
         if (m->scan_scratch) EP_HIP_CHECK(hipFree(m->scan_scratch));
         EP_HIP_CHECK(hipMalloc(&m->scan_scratch, (size_t)need * 2 * sizeof(int32_t)));
-        m->scratch_cap = need * 2;
+        m->scratch_cap = need;
     }
     return EPRECON_OK;
 }
@@ -231,7 +232,7 @@ int ep::ensure_sel(EpMap *m, int64_t rows)
         EP_HIP_CHECK(hipMalloc(&m->sel_aux, (size_t)cap * sizeof(int32_t)));
         m->sel_cap = cap;
     }
-    const int64_t need = scan_scratch_ints(rows) + 8;
+    const int64_t need = scan_scratch_ints(rows);
     if (need > m->sel_scratch_cap) {
         if (m->sel_scratch) EP_HIP_CHECK(hipFree(m->sel_scratch));
         EP_HIP_CHECK(hipMalloc(&m->sel_scratch, (size_t)need * sizeof(int32_t)));
@@ -258,7 +259,7 @@ int ep::map_crop_queue(EpMap *m, const int32_t *cur_coords, const float *cur_fea
     }
     int rc = exclusive_scan_i32(v.flag, cells, v.rank, m->scan_scratch, n_union_dev, st);
     if (rc != EPRECON_OK) return rc;
-    rc = exclusive_scan_i32(m->keep, (int)m->size, m->keep_rank, m->scan_scratch + m->scratch_cap / 2, n_kept_dev, st);
+    rc = exclusive_scan_i32(m->keep, (int)m->size, m->keep_rank, m->scan_scratch + m->scratch_cap, n_kept_dev, st);
     if (rc != EPRECON_OK) return rc;
     hipLaunchKernelGGL(map_emit_kernel, dim3((unsigned)ceil_div(cells, 256)), dim3(256), 0, st, (const int32_t *)v.flag,
                        (const int32_t *)v.rank, (const int32_t *)v.idx_cur, (const int32_t *)v.idx_glob, dim, updated, src_cur, src_glob);

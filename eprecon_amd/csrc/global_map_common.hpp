@@ -20,7 +20,7 @@ struct EpMap {
     int cur = 0;
     int32_t *keep = nullptr, *keep_rank = nullptr;  // [row_cap] 1 = row outside the last crop's FBV; its scan
     int64_t row_cap = 0;
-    int32_t *scan_scratch = nullptr;
+    int32_t *scan_scratch = nullptr;  // [2][scratch_cap]: one half per scan of a crop
     int64_t scratch_cap = 0;
     int32_t *counts_dev = nullptr;  // [4]
     int32_t *counts_host = nullptr;  // pinned [4]

@@ -74,7 +74,7 @@ int ep::target_dense_queue(EpMap *tm, const float *tsdf_gt, const uint8_t *occ_g
     }
     int rc = exclusive_scan_i32(v.flag, cells, v.rank, tm->scan_scratch, n_new_dev, st);
     if (rc != EPRECON_OK) return rc;
-    return exclusive_scan_i32(tm->keep, (int)tm->size, tm->keep_rank, tm->scan_scratch + tm->scratch_cap / 2, n_kept_dev, st);
+    return exclusive_scan_i32(tm->keep, (int)tm->size, tm->keep_rank, tm->scan_scratch + tm->scratch_cap, n_kept_dev, st);
 }
 
 extern "C" {

@@ -7,7 +7,8 @@ namespace ep {
 
 constexpr int kScanTile = 2048;  // elements per workgroup: 256 threads x 8 items
 
-// scratch of a scan over n elements: one int32 per tile (n = 0: none), and the same as a 256-byte aligned segment of a workspace
+// scratch of a scan over n elements: one int32 per tile (n = 0: none), and the same as a 256-byte aligned segment of a workspace.
+// Grows with n: a scratch sized for a capacity serves every shorter scan.
 constexpr int64_t scan_scratch_ints(int64_t n) { return (n + kScanTile - 1) / kScanTile; }
 constexpr size_t scan_scratch_bytes(int64_t n) { return ((size_t)scan_scratch_ints(n) * sizeof(int32_t) + 255) / 256 * 256; }
 

@@ -399,7 +399,11 @@ extern "C" int eprecon_conv_desc_async(const eprecon_conv_desc *d, void *stream)
 extern "C" size_t eprecon_conv_desc_workspace_bytes(const eprecon_conv_desc *d)
 {
     ConvParams p = {};
-    return query_params(p, d) && wide_shape_ok(p) ? wide_workspace_bytes(p) : 0;
+    if (!query_params(p, d)) return 0;
+    // (the two families that take scratch share no shape: the wide pair wants C_out > 64, the direct kernel at most 64)
+    const size_t wide = wide_shape_ok(p) ? wide_workspace_bytes(p) : 0;
+    const size_t direct = select_conv(p).family == kFamDirect16 ? direct16_workspace_bytes(p) : 0;
+    return wide > direct ? wide : direct;
 }
 
 // rows of bn_partial the launch described by `d` writes (= the nblk to hand to

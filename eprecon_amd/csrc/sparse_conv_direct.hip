@@ -26,7 +26,9 @@ bool direct16_ok(const ConvParams &p)
 }
 
 // rows of one BatchNorm summary block of the launch launch_direct16 would make (eprecon_conv_desc_partial_rows)
-int direct16_partial_block_rows(const ConvParams &p) { return persist_ok(p) ? kJobRows : kDirectRows; }
+int direct16_partial_block_rows(const ConvParams &p) { return persist_shape_ok(p) ? kJobRows : kDirectRows; }
+// ... and the workspace it needs: the persistent form's job counters
+size_t direct16_workspace_bytes(const ConvParams &p) { return persist_shape_ok(p) ? kPersistCtrBytes : 0; }
 
 int launch_direct16(const ConvParams &p, hipStream_t st)
 {

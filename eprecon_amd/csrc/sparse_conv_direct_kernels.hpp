@@ -346,7 +346,6 @@ __global__ __launch_bounds__(256) void spconv_direct16_generic_kernel(ConvParams
     constexpr int RT = kRT, G = 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int ROWS = 64 * RT;
-    constexpr int NR = 4 * RT;
     int *sNbr = reinterpret_cast<int *>(smem);                        // [K][ROWS]
     float *sStat = reinterpret_cast<float *>(sNbr + p.K * ROWS);      // [4 waves][3][16 CT]
     const int cpad = 16 * kch;

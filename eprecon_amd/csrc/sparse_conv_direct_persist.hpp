@@ -12,21 +12,19 @@
 // Job counters: same-address device atomics retire one per ~21 ns on this part (tools/probes/atomic_probe.hip), so ONE counter
 // for the launch's ~12k pulls would cost more than the convolution (measured: 278 us).  The jobs are split into 8 contiguous
 // shares — workgroup b pulls from share b % 8, the XCD the dispatcher puts it on when the chip is free; nothing depends on that —
-// each with its own pair (next job, waves done) 64 bytes apart, out of a zero-initialised device array, one set per launch in
-// rotation.  Every wave's LAST pull fails by construction and the last wave of a share to leave puts its pair back to zero, so a
-// set can be reused (HIP graph replays reuse theirs).
-// (kPersistWaves, kJobRows and persist_lds_bytes sit in the selection header: the eligibility rule needs them without the kernel.)
+// each with its own counter (next job) 64 bytes apart.  The counters are the first kPersistCtrBytes of the descriptor's
+// workspace (eprecon_conv_desc_workspace_bytes asks for them) and launch_persist zeroes them on the stream in front of every
+// launch: a launch polls only memory its caller handed it, and a captured launch replays the zeroing with it.  (A fill launch,
+// not the runtime's memset: a captured hipMemsetAsync of more than four bytes replays its pattern correctly ONCE on this runtime
+// and garbage from then on — profiles/r21/memset_node_probe.txt — and a garbage counter skips every job.)
+// (kPersistWaves, kJobRows, the counters' layout and persist_lds_bytes sit in the selection header: the eligibility rule needs them
+// without the kernel.)
 // ---------------------------------------------------------------------------------------------
 #pragma once
-#include <atomic>
-
 #include "sparse_conv_direct_device.hpp"
 
 namespace epconv {
 namespace {
-
-constexpr int kPersistSlots = 512, kShares = 8, kCtrStride = 16;     // (16 uints = 64 B between the pairs of a set)
-__device__ unsigned int g_persist_ctr[kPersistSlots * kShares * kCtrStride];
 
 template <int CT, int KCH, bool TAIL, int G = stage_chunks(KCH)>
 __global__ __launch_bounds__(64 * kPersistWaves) void spconv_persist16_kernel(ConvParams p, int njobs, unsigned int *ctr)
@@ -81,7 +79,7 @@ __global__ __launch_bounds__(64 * kPersistWaves) void spconv_persist16_kernel(Co
     const unsigned per = ((unsigned)njobs + kShares - 1) / kShares;
     const unsigned job_lo = share * per, job_hi = min(job_lo + per, (unsigned)njobs);
     unsigned job = 0;
-    if (lane == 0) job = atomicAdd(&ctr[0], 1u);
+    if (lane == 0) job = atomicAdd(ctr, 1u);
     job = (unsigned)__builtin_amdgcn_readfirstlane((int)job) + job_lo;
     while (job < job_hi) {
         const int row0 = (int)job * ROWS;
@@ -109,7 +107,7 @@ __global__ __launch_bounds__(64 * kPersistWaves) void spconv_persist16_kernel(Co
         }
         live = (unsigned)__builtin_amdgcn_readfirstlane((int)live);
         unsigned next = 0;
-        if (lane == 0) next = atomicAdd(&ctr[0], 1u);        // the next job's index travels while this one runs
+        if (lane == 0) next = atomicAdd(ctr, 1u);            // the next job's index travels while this one runs
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the window is written before any lane reads another lane's entry
 
         constexpr int NS = CTM == 1 ? 2 : 1;       // (two accumulator sets when a row tile has one full column tile: see the template kernel)
@@ -252,30 +250,23 @@ __global__ __launch_bounds__(64 * kPersistWaves) void spconv_persist16_kernel(Co
         }
         job = (unsigned)__builtin_amdgcn_readfirstlane((int)next) + job_lo;
     }
-    if (lane == 0) {
-        // workgroups of this share: b = share, share + 8, ... < gridDim.x
-        const unsigned mates = (gridDim.x - share + kShares - 1) / kShares;
-        const unsigned done = atomicAdd(&ctr[1], 1u);
-        if (done == mates * (unsigned)kPersistWaves - 1u) {      // every wave of the share has made its last (failing) pull
-            __hip_atomic_store(&ctr[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&ctr[1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
 }
 
 template <int CT, int KCH, bool TAIL>
 int launch_persist(const ConvParams &p, hipStream_t st)
 {
+    // (the caller sized its summaries for 32-row jobs: no other kernel can stand in for a launch that came without its counters)
+    if (!persist_ok(p)) return EPRECON_ERR_WORKSPACE;
     static bool attr_set = false;
     auto kern = spconv_persist16_kernel<CT, KCH, TAIL>;
     if (!attr_set) {
         EP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
         attr_set = true;
     }
-    static unsigned int *ctr_base = nullptr;
-    if (!ctr_base) EP_HIP_CHECK(hipGetSymbolAddress(reinterpret_cast<void **>(&ctr_base), HIP_SYMBOL(g_persist_ctr)));
-    static std::atomic<unsigned> slot{0};
-    unsigned int *ctr = ctr_base + (size_t)kShares * kCtrStride * (slot.fetch_add(1u) % (unsigned)kPersistSlots);
+    unsigned int *ctr = static_cast<unsigned int *>(p.ws);
+    const FillRegion zero = {ctr, kPersistCtrBytes, 0u};
+    const int rc = multi_fill(&zero, 1, st);
+    if (rc != EPRECON_OK) return rc;
     const int njobs = ceil_div(p.n_out, kJobRows);
     const int grid = max(kShares, min(device_cus(), ceil_div(njobs, kPersistWaves)));    // (every share has a workgroup)
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * kPersistWaves), persist_lds_bytes(p), st, p, njobs, ctr);

@@ -12,6 +12,8 @@ using namespace ep;
 constexpr int kRT = 2;   // 16-row tiles per wave
 constexpr int kPersistWaves = 8;            // waves of the persistent form's one workgroup per CU,
 constexpr int kJobRows = 16 * kRT;          // each pulling jobs of this many rows (the rows of its BatchNorm summary blocks)
+constexpr int kShares = 8, kCtrStride = 16;  // its job counters: one per share of the jobs, 16 uints = 64 B apart,
+constexpr size_t kPersistCtrBytes = (size_t)kShares * kCtrStride * sizeof(unsigned int);   // at the head of ConvParams::ws
 constexpr size_t kLdsBytes = 160 * 1024;
 
 // chunks per stage for a layer of KCH chunks: the stages of an offset are KCH / G
@@ -51,7 +53,7 @@ static int device_cus()
     return n;
 }
 
-// The switches of the selection, read at every launch: tests flip them.  (The fifth, EPRECON_CONV_PERSIST, is read by persist_ok,
+// The switches of the selection, read at every launch: tests flip them.  (The fifth, EPRECON_CONV_PERSIST, is read by persist_shape_ok,
 // which the family selection asks at every convolution call: it reads nothing else while the opt-in is off.)
 struct DirectSwitches {
     // EPRECON_CONV_TAIL8=0: C_out = 16 m + 8 on padded 16-column tiles (the round-5 form)
@@ -84,7 +86,8 @@ constexpr int kPersistMinRows = 8192;
 // per-tile kernel on the cfg4-leading layer (48 -> 24 on 320,868 rows: 203.6 against 203.3 us) and 10-19 % slower on the
 // 198k-row layers, whose 24.2 jobs per CU are 2.02 per wave of three resident ones — a third round for 1 % of the jobs
 // (profiles/r06/conv_forms_ab.txt).
-static bool persist_ok(const ConvParams &p)
+// Shape rule, independent of the workspace: the selection and the summary-block rows ask this one.
+static bool persist_shape_ok(const ConvParams &p)
 {
     const int kch = (p.Cin + 15) / 16, ct = (p.Cout + 15) / 16;
     const bool rem8 = p.Cout - 16 * (ct - 1) <= 8;
@@ -96,6 +99,11 @@ static bool persist_ok(const ConvParams &p)
     // the launcher's compile-time guards are this bound at rem8 = true / false)
     if (kch * ((rem8 ? ct - 1 : ct) * 1024 + (rem8 ? 512 : 0)) > 4864) return false;
     return p.n_out >= kPersistMinRows;
+}
+// ... and with the job counters the launch needs in its workspace (launch_persist refuses the launch without them)
+static bool persist_ok(const ConvParams &p)
+{
+    return persist_shape_ok(p) && p.ws && (reinterpret_cast<uintptr_t>(p.ws) & 3) == 0 && p.ws_bytes >= kPersistCtrBytes;
 }
 
 // One instantiation: spconv_persist16_kernel<CT, KCH, tail> when `persist`, spconv_direct16_generic_kernel<CT> when g == 0,
@@ -114,8 +122,8 @@ static DirectForm select_direct_form(const ConvParams &p, const DirectSwitches &
     if (kch > 6) return f;                      // any chunk count: run-time indices
     const int g0 = stage_chunks(kch);
     f.g = g0;
-    // 1. the persistent form (its tail rule is persist_ok's: with the 4x4x1 form switched off it is not eligible)
-    if (persist_ok(p)) {
+    // 1. the persistent form (its tail rule is persist_shape_ok's: with the 4x4x1 form switched off it is not eligible)
+    if (persist_shape_ok(p)) {
         f.persist = true;
         f.tail = direct_tail(p, sw);
         return f;

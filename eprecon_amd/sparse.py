@@ -590,8 +590,10 @@ def conv_call(x, weight, nbr=None, bias=None, out=None, relu=False, accumulate=F
             d.packed_weight16 = keep[-1].data_ptr()
     # scratch of the kernel pair that reduces partial sums across workgroups: the library says how much the described launch
     # wants.  Asked only where the answer can be other than 0: wide_shape_ok (csrc/sparse_conv_wide.hip) needs K = 27, a
-    # kernel map, packed_weight, at least 96 input channels and no LayerNorm
-    if kvol == 27 and cin >= 96 and ln is None and d.packed_weight and d.nbr:
+    # kernel map, packed_weight, at least 96 input channels and no LayerNorm; the opt-in persistent form (its job counters)
+    # needs EPRECON_CONV_PERSIST=1 and packed_weight16
+    if (kvol == 27 and cin >= 96 and ln is None and d.packed_weight and d.nbr) or (
+            d.packed_weight16 and os.environ.get("EPRECON_CONV_PERSIST", "")[:1] == "1"):
         need = int(lib.eprecon_conv_desc_workspace_bytes(ctypes.byref(d)))
         if need:
             keep.append(_lib.workspace(need, x.device))

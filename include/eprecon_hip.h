@@ -234,7 +234,10 @@ int eprecon_hash_status(const void *table, void *stream);
 size_t eprecon_unique_workspace_bytes(int64_t n);
 /* exclusive prefix sum of int32 (the device scan behind every compaction / unique numbering of the path: torch.nonzero,
  * boolean-mask indexing and torch.unique at models/neucon_network.py:298-318,454-507, ops/torchsparse_utils.py:20-22):
- * out[i] = in[0] + ... + in[i - 1]; *total (optional, device) = the sum of all n; scratch int32[ceil(n / 2048)] */
+ * out[i] = in[0] + ... + in[i - 1]; *total (optional, device) = the sum of all n; scratch
+ * int32[eprecon_exclusive_scan_scratch_ints(n)]: the tile sums one launch of the call leaves for the next.  The call cannot
+ * see the size of what it is given: the query is the contract.  A call touches no memory but what it is handed. */
+size_t eprecon_exclusive_scan_scratch_ints(int64_t n);
 int eprecon_exclusive_scan_async(const int32_t *in, int64_t n, int32_t *out, int32_t *total, int32_t *scratch, void *stream);
 int eprecon_unique_coords_async(const int32_t *coords, int64_t n, int quantum, void *table,
                                 uint32_t capacity, int32_t *inverse, int32_t *unique_coords,
@@ -365,7 +368,9 @@ typedef struct eprecon_conv_desc {
     const float *packed_weight16;
     /* scratch for kernels that reduce partial sums across workgroups (medium lists with wide channels, 3x3x3, with
      * packed_weight): eprecon_conv_desc_workspace_bytes(desc) bytes (0: none needed); without it those shapes stay on the
-     * short-list kernel */
+     * short-list kernel.  With EPRECON_CONV_PERSIST=1 the query also answers the job counters of the persistent kernel (512
+     * bytes, zeroed by the launch): a launch that kernel would take WITHOUT them returns EPRECON_ERR_WORKSPACE — its
+     * summaries are per 32-row job, no other kernel can stand in */
     void *workspace; size_t workspace_bytes;
     /* BatchNorm of the OUTPUT without a finalize launch (round 6; replaces bn_partial + eprecon_batchnorm_finalize_affine_async
      * between two layers, models/modules.py:15-29,313-399): the launch adds per-channel sums of the stored values to an

@@ -293,3 +293,13 @@ def test_workspace_sizes_are_the_recorded_ones():
         want = golden[name][",".join(map(str, args))]
         got = getattr(lib, name)(*args)
         assert got == want, (name, args, got, want)
+
+
+def test_scan_scratch_query_is_the_documented_rule():
+    """eprecon_exclusive_scan_scratch_ints, the contract of the scan's scratch: one int32 per tile of 2,048 elements, one rule
+    for every length; nothing where there is no scan"""
+    from eprecon_amd import _lib
+    lib = _lib.load()
+    for n in _SCAN_EDGES + [100003, 320868, 2 ** 31 - 1]:
+        assert lib.eprecon_exclusive_scan_scratch_ints(n) == (n + 2047) // 2048, n
+    assert lib.eprecon_exclusive_scan_scratch_ints(-1) == 0 and lib.eprecon_exclusive_scan_scratch_ints(2 ** 31) == 0

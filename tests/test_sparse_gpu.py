@@ -29,24 +29,40 @@ def test_hash_build_query(n, stride):
     assert np.array_equal(g.query(dev(q)).cpu().numpy(), OS.Index(c).lookup(q))
 
 
+def _scan_scratch_ints(lib, n):
+    """what the library asks for a scan over n elements: the only contract there is for the scratch"""
+    return int(lib.eprecon_exclusive_scan_scratch_ints(n))
+
+
+def _scan(lib, dx, n, out, tot, scratch, stream=None):
+    from eprecon_amd import _lib
+    _lib.check(lib.eprecon_exclusive_scan_async(_lib.ptr(dx), n, _lib.ptr(out), _lib.ptr(tot), _lib.ptr(scratch),
+                                                _lib.current_stream() if stream is None else stream.cuda_stream),
+               "eprecon_exclusive_scan_async")
+
+
+def _scan_case(n, seed=None):
+    x = np.random.default_rng(n if seed is None else seed).integers(0, 9, n).astype(np.int32)
+    return x, np.concatenate([[0], np.cumsum(x[:-1], dtype=np.int64)]).astype(np.int32)
+
+
+SCAN_GUARD = 0x5ca7c4ed
+
+
 @pytest.mark.parametrize("n", [1, 63, 2049, 8192, 8193, 16385, 32768, 32769, 100003, 320868, 2500001])
-def test_device_scan_all_forms(monkeypatch, n):
-    """the exclusive scan behind every compaction: one workgroup / one pass up to 32,768 elements, one decoupled look-back launch
-    beyond (round 6; EPRECON_SCAN_LOOKBACK=0: tile sums + apply) — against numpy, the grand total included, twice (the
-    look-back's state words clean themselves), and 70 launches in a row (more than the 64 state sets in rotation)"""
+def test_device_scan_all_forms(n):
+    """the exclusive scan behind every compaction: one workgroup / one pass up to 32,768 elements, tile sums + apply beyond —
+    against numpy, the grand total included, twice, and 70 launches in a row into the same scratch (a call keeps no state)"""
     from eprecon_amd import _lib
     lib = _lib.load()
-    rng = np.random.default_rng(n)
-    x = rng.integers(0, 9, n).astype(np.int32)
-    want = np.concatenate([[0], np.cumsum(x[:-1], dtype=np.int64)]).astype(np.int32)
+    x, want = _scan_case(n)
     dx = dev(x)
-    scratch = torch.empty((n + 2047) // 2048, dtype=torch.int32, device="cuda")
+    scratch = torch.empty(_scan_scratch_ints(lib, n), dtype=torch.int32, device="cuda")
 
     def run():
         out = torch.full((n,), -7, dtype=torch.int32, device="cuda")
         tot = torch.full((1,), -7, dtype=torch.int32, device="cuda")
-        _lib.check(lib.eprecon_exclusive_scan_async(_lib.ptr(dx), n, _lib.ptr(out), _lib.ptr(tot), _lib.ptr(scratch),
-                                                    _lib.current_stream()), "eprecon_exclusive_scan_async")
+        _scan(lib, dx, n, out, tot, scratch)
         return out.cpu().numpy(), int(tot.item())
     for _ in range(2):
         got, tot = run()
@@ -55,31 +71,87 @@ def test_device_scan_all_forms(monkeypatch, n):
         for _ in range(70):
             got, tot = run()
         assert np.array_equal(got, want) and tot == int(x.sum())
-        monkeypatch.setenv("EPRECON_SCAN_LOOKBACK", "0")
-        got, tot = run()
-        assert np.array_equal(got, want) and tot == int(x.sum())
 
 
-@pytest.mark.parametrize("n,lookback", [(32769, True), (32769, False), (4096 * 2048 + 1, True)])
-def test_device_scan_stays_inside_its_scratch(monkeypatch, n, lookback):
-    """the scratch is exactly the documented ceil(n / 2048) int32 with 64 guard words behind it, at the smallest length that
-    reaches each long form: the look-back launch (takes no scratch), tile sums + scan_apply<true> (17 tiles), and above 4,096
-    tiles tile sums + scan_sums_inplace + scan_apply<false> (4,097 tiles; the look-back does not go that far)"""
+@pytest.mark.parametrize("n", [32769, 100003, 4096 * 2048 + 1])
+def test_device_scan_stays_inside_its_scratch(n):
+    """the scratch is exactly what eprecon_exclusive_scan_scratch_ints answers, with 64 guard words behind it, at the smallest
+    length that reaches each long form: tile sums + scan_apply<true> (17 tiles; 49 tiles), and above 4,096 tiles tile sums +
+    scan_sums_inplace + scan_apply<false> (4,097 tiles).  The whole buffer starts as the guard pattern, and a second launch
+    into the same buffer meets what the first one left: a scan depends on nothing it finds in its scratch."""
     from eprecon_amd import _lib
     lib = _lib.load()
-    if not lookback:
-        monkeypatch.setenv("EPRECON_SCAN_LOOKBACK", "0")
-    x = np.random.default_rng(n).integers(0, 9, n).astype(np.int32)
-    want = np.concatenate([[0], np.cumsum(x[:-1], dtype=np.int64)]).astype(np.int32)
-    tiles, guard = (n + 2047) // 2048, 0x5ca7c4ed
-    buf = torch.full((tiles + 64,), guard, dtype=torch.int32, device="cuda")
+    x, want = _scan_case(n)
+    tiles = _scan_scratch_ints(lib, n)
+    assert tiles >= (n + 2047) // 2048
+    buf = torch.full((tiles + 64,), SCAN_GUARD, dtype=torch.int32, device="cuda")
     dx = dev(x)
-    out = torch.full((n,), -7, dtype=torch.int32, device="cuda")
-    tot = torch.full((1,), -7, dtype=torch.int32, device="cuda")
-    _lib.check(lib.eprecon_exclusive_scan_async(_lib.ptr(dx), n, _lib.ptr(out), _lib.ptr(tot), _lib.ptr(buf),
-                                                _lib.current_stream()), "eprecon_exclusive_scan_async")
-    assert bool((buf[tiles:] == guard).all())
-    assert np.array_equal(out.cpu().numpy(), want) and int(tot.item()) == int(x.sum()) < 2 ** 27
+    for _ in range(2):
+        out = torch.full((n,), -7, dtype=torch.int32, device="cuda")
+        tot = torch.full((1,), -7, dtype=torch.int32, device="cuda")
+        _scan(lib, dx, n, out, tot, buf)
+        assert bool((buf[tiles:] == SCAN_GUARD).all())
+        assert np.array_equal(out.cpu().numpy(), want) and int(tot.item()) == int(x.sum()) < 2 ** 27
+
+
+def test_device_scans_on_two_streams_keep_their_state_apart():
+    """two streams, each with its own input (17 and 49 tiles), scratch and outputs: 70 scans per stream, queued
+    alternately from the host, every one into a scratch refilled with the guard pattern on its own stream.  Every output and
+    total is compared on the device; one host read per stream at the end."""
+    from eprecon_amd import _lib
+    lib = _lib.load()
+    torch.cuda.synchronize()
+    lanes = []
+    for n in (32769, 100003):
+        x, want = _scan_case(n)
+        st = torch.cuda.Stream()
+        with torch.cuda.stream(st):
+            lanes.append(dict(n=n, st=st, dx=dev(x), want=dev(want), total=int(x.sum()),
+                              scratch=torch.empty(_scan_scratch_ints(lib, n), dtype=torch.int32, device="cuda"),
+                              out=torch.empty(n, dtype=torch.int32, device="cuda"),
+                              tot=torch.empty(1, dtype=torch.int32, device="cuda"),
+                              ok=torch.ones((), dtype=torch.bool, device="cuda")))
+    for _ in range(70):
+        for a in lanes:
+            with torch.cuda.stream(a["st"]):
+                a["scratch"].fill_(SCAN_GUARD)
+                a["out"].fill_(-7)
+                a["tot"].fill_(-7)
+                _scan(lib, a["dx"], a["n"], a["out"], a["tot"], a["scratch"], a["st"])
+                a["ok"] &= (a["out"] == a["want"]).all() & (a["tot"][0] == a["total"])
+    for a in lanes:
+        with torch.cuda.stream(a["st"]):
+            assert bool(a["ok"].item()), a["n"]
+    torch.cuda.synchronize()
+
+
+def test_device_scan_replays_under_a_graph():
+    """two scans (17 and 49 tiles, a scratch each) captured back to back in one graph on one stream, replayed three times with
+    the inputs overwritten in between: a replay depends on nothing the one before it left in the scratch"""
+    from eprecon_amd import _lib
+    lib = _lib.load()
+    ns = (32769, 100003)
+    cases = [[_scan_case(n, seed) for n in ns] for seed in (11, 12)]
+    dx = [dev(x) for x, _ in cases[0]]
+    scratch = [torch.empty(_scan_scratch_ints(lib, n), dtype=torch.int32, device="cuda") for n in ns]
+    out = [torch.full((n,), -7, dtype=torch.int32, device="cuda") for n in ns]
+    tot = [torch.full((1,), -7, dtype=torch.int32, device="cuda") for n in ns]
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for i, n in enumerate(ns):
+            _scan(lib, dx[i], n, out[i], tot[i], scratch[i])
+    for replay in range(3):
+        case = cases[replay % 2]
+        for i in range(2):
+            dx[i].copy_(dev(case[i][0]))
+            out[i].fill_(-7)
+            tot[i].fill_(-7)
+        graph.replay()
+        torch.cuda.synchronize()
+        for i in range(2):
+            x, want = case[i]
+            assert np.array_equal(out[i].cpu().numpy(), want) and int(tot[i].item()) == int(x.sum())
 
 
 def test_hash_rejects_out_of_range_keys():
@@ -373,13 +445,46 @@ def test_direct_kernel_forms_agree(monkeypatch, form, cin, cout):
         tot_m2 = (m2 + cnt * (mean - tot_mean) ** 2).sum(0)
         assert np.abs(tot_mean - want.mean(0)).max() < 1e-4 and np.abs(tot_m2 / n - want.var(0)).max() < 1e-3
     assert np.abs(y0 - y1).max() < 1e-4
-    # the persistent form's counters come back to zero: a second launch on the same set (512 launches later) would hang or
-    # skip rows otherwise — run it enough times to wrap the rotation once
+    # the persistent form zeroes its own job counters, the head of the stream's grow-only workspace: dirty counters would make
+    # it skip every row or run past the list — a launch into a workspace full of 0xFF, and one more into what that launch left
     if persist_takes_it:
-        for _ in range(520):
-            SP.conv_stats(dx, dw, nbr_d, in_affine=(dev(sc), dev(sh), True), bias=db)
+        from eprecon_amd import _lib
+        _lib.workspace(512, torch.device("cuda", torch.cuda.current_device())).fill_(0xFF)
         y2, _ = run()
         assert np.array_equal(y1, y2)
+        y2, _ = run()
+        assert np.array_equal(y1, y2)
+
+
+def test_persistent_form_asks_for_its_counters(monkeypatch):
+    """EPRECON_CONV_PERSIST=1, 48 -> 24 on the shortest list the form takes (8,192 rows): the workspace query answers its job
+    counters and the summaries are per 32-row job; the same descriptor WITHOUT the workspace is refused (EPRECON_ERR_WORKSPACE)
+    before anything is launched — it must not end up on the 128-row kernel, whose summaries the caller did not size.  One row
+    fewer and the launch is the per-tile kernel's: no workspace, 128-row blocks.  (EPRECON_CONV_SPLITK=0: up to 256 workgroups
+    of 128 rows the split-K kernel goes first, so the shortest list the form takes reaches the direct family only without it.)"""
+    import ctypes
+    from eprecon_amd import _lib
+    from eprecon_amd import sparse as SP
+    lib = _lib.load()
+    monkeypatch.setenv("EPRECON_CONV_PERSIST", "1")
+    monkeypatch.setenv("EPRECON_CONV_SPLITK", "0")
+    g = torch.Generator().manual_seed(3)
+    for n in (8192, 8191):
+        nbr = torch.randint(-1, n, (27, n), generator=g, dtype=torch.int32).cuda()
+        x, w = torch.randn((n, 48), generator=g).cuda(), (torch.randn((27, 48, 24), generator=g) / 36).cuda()
+        out = torch.full((n, 24), -7.0, device="cuda")
+        _, part, d, keep = SP.conv_call(x, w, nbr, out=out, stats=True, launch=False)
+        need = int(lib.eprecon_conv_desc_workspace_bytes(ctypes.byref(d)))
+        if n < 8192:
+            assert need == 0 and part.shape[0] == (n + 127) // 128
+            continue
+        assert need >= 512 and d.workspace and d.workspace_bytes >= need and part.shape[0] == n // 32
+        d.workspace, d.workspace_bytes = None, 0
+        assert int(lib.eprecon_conv_desc_workspace_bytes(ctypes.byref(d))) == need         # the query does not depend on it
+        assert int(lib.eprecon_conv_desc_partial_rows(ctypes.byref(d))) == n // 32
+        with pytest.raises(_lib.EpreconError, match="error -2"):
+            _lib.check(lib.eprecon_conv_desc_async(ctypes.byref(d), _lib.current_stream()), "eprecon_conv_desc_async")
+        assert bool((out == -7.0).all())
 
 
 BF16X3_BUDGET = 2.0 ** -14      # of the term-magnitude sum  sum_k |a_k| |w_k|  of an output (DESIGN.md 3b: 3 * 2^-16 by construction)
