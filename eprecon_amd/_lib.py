@@ -141,6 +141,10 @@ SIGNATURES = {
     "eprecon_marching_cubes_emit_masked_async": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "eprecon_render_depth_workspace_bytes": (_sz, [_i64]),
     "eprecon_render_depth_async": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _f, _f, _f, _i, _vp, _i64, _vp, _sz, _vp]),
+    "eprecon_render_visibility_workspace_bytes": (_sz, [_i64]),
+    "eprecon_render_visibility_async": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _f, _f, _f, _i, _vp, _i64, _vp, _sz, _vp]),
+    "eprecon_render_resolve_async": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _c.c_int32, _vp, _vp,
+                                          _c.c_int32, _vp, _vp, _c.c_double, _i, _i, _i, _vp, _vp]),
     "eprecon_depth_metrics_workspace_bytes": (_sz, [_i]),
     "eprecon_depth_metrics_async": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _sz, _vp]),
     "eprecon_point_bounds_async": (_i, [_vp, _i64, _vp, _vp, _vp]),

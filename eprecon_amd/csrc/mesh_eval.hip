@@ -7,165 +7,37 @@
 //   voxel_down_sample   open3d VoxelDownSample, deterministic and in voxel-key order
 //   nn_search        nn_correspondance: exact nearest neighbour through a uniform grid, smallest index on ties
 //
-// Rasteriser: one thread per (triangle, view) in a 2D grid (y = view) transforms its triangle into the camera (fp64),
-// culls it, and sizes its pixel box.  A box of at most kSmallBox pixels is walked by that thread; a larger one goes to a
-// queue that a second launch walks with a whole wave per entry (64 lanes stride the box), so that the few triangles near
-// the camera do not serialise one thread over thousands of pixels.  Coverage is decided per pixel in camera space by the
-// signs of the ray's triple products with the three edge planes through the camera centre — exact for triangles that
-// cross the near plane or lie partly behind the camera, with no clipping of the triangle; only its pixel box is taken from
-// the part in front of z = znear (a box of the whole image for every triangle that crosses the camera plane made those
-// few hundred triangles per view the largest cost of a room scene).
-// The depth is the ray / plane intersection.  The z-buffer is the output itself: filled with +inf bits, lowered by
+// Rasteriser: csrc/mesh_raster.hpp (one thread per (triangle, view), a wave per large pixel box, fp64 edge-plane coverage,
+// ray / plane depth).  The z-buffer is the output itself: filled with +inf bits, lowered by
 // atomicMin on the (positive) fp32 bit pattern, +inf turned into 0 at the end — a min, so bit-identical run to run.
 #include <math.h>
 
 #include <algorithm>
 
+#include "mesh_raster.hpp"
 #include "scan.hpp"
 
 namespace {
 using namespace ep;
-
-constexpr int kSmallBox = 64;          // pixel boxes up to this size stay with their (triangle, view) thread
-constexpr unsigned kInfBits = 0x7F800000u;
+using namespace ep_raster;
 
 // ----------------------------------------------------------------------------------------------- depth rasteriser
+// (setup, coverage, depth and the two walks: mesh_raster.hpp, shared with the visibility buffer of mesh_render.hip)
 
-struct RenderParams {
-    const float *verts;
-    const int32_t *faces;
-    const double *cams;      // K[9], K^-1[9], per view w2c[12]
-    int64_t n_verts, n_faces;
-    int n_views, height, width;
-    float pixel_center, znear, zfar;
-    int cull_back;
-    unsigned *zbuf;          // [V,H,W] fp32 bits
-    unsigned *queue_count;
-    unsigned long long *queue;
-    int64_t queue_capacity;
+struct DepthSink {
+    unsigned *zbuf;
+    int height, width;
+    __device__ __forceinline__ void operator()(int view, int64_t, int r, int c, unsigned bits) const
+    {
+        unsigned *dst = zbuf + ((size_t)view * height + r) * width + c;
+        if (bits < *dst) atomicMin(dst, bits);
+    }
 };
 
-struct TriSetup {
-    double e0[3], e1[3], e2[3];   // edge-plane normals a x b, b x c, c x a
-    double n[3], nd;              // plane normal (b-a) x (c-a) and n . a
-    int c_lo, c_hi, r_lo, r_hi;   // pixel box (inclusive)
-};
-
-__device__ __forceinline__ void cross3(const double *a, const double *b, double *o)
-{
-    o[0] = a[1] * b[2] - a[2] * b[1];
-    o[1] = a[2] * b[0] - a[0] * b[2];
-    o[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-__device__ __forceinline__ double dot3(const double *a, const double *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-
-__device__ __forceinline__ int clamp_pix(double v, int hi) { return (int)fmin(fmax(v, -1.0), (double)hi + 1.0); }
-
-// false: the triangle draws nothing in this view
-__device__ bool tri_setup(const RenderParams &P, int view, int64_t tri, TriSetup &T)
-{
-    const int32_t i0 = P.faces[3 * tri], i1 = P.faces[3 * tri + 1], i2 = P.faces[3 * tri + 2];
-    if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= P.n_verts || i1 >= P.n_verts || i2 >= P.n_verts) return false;
-    const double *K = P.cams, *M = P.cams + 18 + 12 * (size_t)view;
-    double v[3][3];
-    const int32_t id[3] = {i0, i1, i2};
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double x = P.verts[3 * (size_t)id[k]], y = P.verts[3 * (size_t)id[k] + 1], z = P.verts[3 * (size_t)id[k] + 2];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) v[k][r] = ((M[4 * r] * x + M[4 * r + 1] * y) + M[4 * r + 2] * z) + M[4 * r + 3];
-    }
-    const double zmin = fmin(v[0][2], fmin(v[1][2], v[2][2])), zmax = fmax(v[0][2], fmax(v[1][2], v[2][2]));
-    if (zmax < (double)P.znear || zmin > (double)P.zfar) return false;
-    const double u[3] = {v[1][0] - v[0][0], v[1][1] - v[0][1], v[1][2] - v[0][2]};
-    const double w[3] = {v[2][0] - v[0][0], v[2][1] - v[0][1], v[2][2] - v[0][2]};
-    cross3(u, w, T.n);
-    T.nd = dot3(T.n, v[0]);
-    if (T.nd == 0.0) return false;                     // degenerate, or its plane passes through the camera
-    if (P.cull_back && !(T.nd < 0.0)) return false;    // back face
-    cross3(v[0], v[1], T.e0);
-    cross3(v[1], v[2], T.e1);
-    cross3(v[2], v[0], T.e2);
-    // pixel box: the projection of the part of the triangle with z >= znear (the corners in front, plus the points where
-    // the edges cross z = znear), one pixel of slack — only the box is clipped, the exact per-pixel test decides coverage
-    const double pc = (double)P.pixel_center, zn = (double)P.znear;
-    double umin = 1e300, umax = -1e300, vmin = 1e300, vmax = -1e300;
-    auto add = [&](const double *q) {
-        const double iz = 1.0 / q[2];
-        const double px = ((K[0] * q[0] + K[1] * q[1]) + K[2] * q[2]) * iz;
-        const double py = ((K[3] * q[0] + K[4] * q[1]) + K[5] * q[2]) * iz;
-        umin = fmin(umin, px); umax = fmax(umax, px); vmin = fmin(vmin, py); vmax = fmax(vmax, py);
-    };
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double *a = v[k], *b = v[(k + 1) % 3];
-        if (a[2] >= zn) add(a);
-        if ((a[2] < zn) != (b[2] < zn)) {
-            const double t = (zn - a[2]) / (b[2] - a[2]);
-            const double q[3] = {a[0] + t * (b[0] - a[0]), a[1] + t * (b[1] - a[1]), zn};
-            add(q);
-        }
-    }
-    T.c_lo = max(clamp_pix(ceil(umin - pc) - 1.0, P.width), 0);
-    T.c_hi = min(clamp_pix(floor(umax - pc) + 1.0, P.width), P.width - 1);
-    T.r_lo = max(clamp_pix(ceil(vmin - pc) - 1.0, P.height), 0);
-    T.r_hi = min(clamp_pix(floor(vmax - pc) + 1.0, P.height), P.height - 1);
-    return T.c_lo <= T.c_hi && T.r_lo <= T.r_hi;
-}
-
-__device__ __forceinline__ void shade(const RenderParams &P, const TriSetup &T, int view, int r, int c)
-{
-    const double *Ki = P.cams + 9;
-    const double pu = (double)c + (double)P.pixel_center, pv = (double)r + (double)P.pixel_center;
-    const double d[3] = {(Ki[0] * pu + Ki[1] * pv) + Ki[2], (Ki[3] * pu + Ki[4] * pv) + Ki[5], (Ki[6] * pu + Ki[7] * pv) + Ki[8]};
-    const double s0 = dot3(T.e0, d), s1 = dot3(T.e1, d), s2 = dot3(T.e2, d);
-    const bool covered = (s0 >= 0.0 && s1 >= 0.0 && s2 >= 0.0) || (s0 <= 0.0 && s1 <= 0.0 && s2 <= 0.0);
-    if (!covered) return;
-    const double den = dot3(T.n, d);
-    if (den == 0.0) return;
-    const double z = T.nd / den * d[2];
-    if (!(z >= (double)P.znear && z <= (double)P.zfar)) return;
-    const unsigned bits = __float_as_uint((float)z);
-    unsigned *dst = P.zbuf + ((size_t)view * P.height + r) * P.width + c;
-    if (bits < *dst) atomicMin(dst, bits);
-}
-
-__global__ __launch_bounds__(256) void render_tri_kernel(RenderParams P)
-{
-    const int64_t tri = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int view = blockIdx.y;
-    if (tri >= P.n_faces) return;
-    TriSetup T;
-    if (!tri_setup(P, view, tri, T)) return;
-    const int bw = T.c_hi - T.c_lo + 1, area = bw * (T.r_hi - T.r_lo + 1);
-    if (area > kSmallBox) {
-        const unsigned slot = atomicAdd(P.queue_count, 1u);
-        if ((int64_t)slot < P.queue_capacity) {
-            P.queue[slot] = ((unsigned long long)view << 32) | (unsigned long long)tri;
-            return;
-        }
-        // (queue full: this thread walks the box itself — slower, same result)
-    }
-    for (int k = 0; k < area; ++k) shade(P, T, view, T.r_lo + k / bw, T.c_lo + k % bw);
-}
+__global__ __launch_bounds__(256) void render_tri_kernel(RenderParams P) { raster_tri(P, DepthSink{P.zbuf, P.height, P.width}); }
 
 // one wave per queued (view, triangle): its 64 lanes stride the pixel box
-__global__ __launch_bounds__(256) void render_queue_kernel(RenderParams P)
-{
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t n_waves = (int64_t)gridDim.x * (256 / kWave);
-    const int64_t count = min((int64_t)*P.queue_count, P.queue_capacity);
-    for (int64_t e = (int64_t)blockIdx.x * (256 / kWave) + threadIdx.x / kWave; e < count; e += n_waves) {
-        const unsigned long long q = P.queue[e];
-        const int view = (int)(q >> 32);
-        const int64_t tri = (int64_t)(q & 0xffffffffull);
-        TriSetup T;
-        if (!tri_setup(P, view, tri, T)) continue;    // (wave-uniform: every lane set up the same triangle)
-        const int bw = T.c_hi - T.c_lo + 1, area = bw * (T.r_hi - T.r_lo + 1);
-        for (int k = lane; k < area; k += kWave) shade(P, T, view, T.r_lo + k / bw, T.c_lo + k % bw);
-    }
-}
+__global__ __launch_bounds__(256) void render_queue_kernel(RenderParams P) { raster_queue(P, DepthSink{P.zbuf, P.height, P.width}); }
 
 __global__ __launch_bounds__(256) void render_finish_kernel(unsigned *zbuf, int64_t n)
 {
@@ -468,18 +340,14 @@ __global__ __launch_bounds__(256) void nn_query_kernel(NnGrid G, const float4 *s
 
 extern "C" {
 
-size_t eprecon_render_depth_workspace_bytes(int64_t queue_capacity)
-{
-    return 256 + align_up((size_t)(queue_capacity > 0 ? queue_capacity : 0) * 8, 256);
-}
+size_t eprecon_render_depth_workspace_bytes(int64_t queue_capacity) { return raster_workspace_bytes(queue_capacity); }
 
 int eprecon_render_depth_async(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const double *cams,
                                int n_views, int height, int width, float pixel_center, float znear, float zfar, int cull_back,
                                float *depth_out, int64_t queue_capacity, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!cams || !depth_out || !workspace || n_views < 1 || n_views > 65535 || height < 1 || width < 1 || n_faces < 0 ||
-        n_verts < 0 || n_faces > 0x7fffffffll || queue_capacity < 0 || !(znear > 0.0f) || !(zfar >= znear) ||
-        (n_faces > 0 && (!verts || !faces)))
+    if (!depth_out || !workspace ||
+        !raster_args_ok(verts, n_verts, faces, n_faces, cams, n_views, height, width, znear, zfar, queue_capacity))
         return EPRECON_ERR_ARG;
     if (workspace_bytes < eprecon_render_depth_workspace_bytes(queue_capacity)) return EPRECON_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;

@@ -1,12 +1,17 @@
 """Panoptic scoring of a saved scene: PQ, SQ, RQ per class (all / things / stuff) and semantic IoU / mIoU.
 
     python -m eprecon_amd.panoptic_score --pred DIR --scenes FILE (--gt DIR | --info DIR) [--threshold 0.5] [--out FILE]
+    python -m eprecon_amd.panoptic_score --pred DIR --scenes FILE --views DATA_PATH --info DIR --gt_mesh DIR [--every 10]
+                                         [--size W H]
 
 --pred holds the <scene>.npz files SaveScene wrote (either form).  With --info DIR the sites are the vertices of
 DIR/<scene>_{vert,sem_label,ins_label}.npy (the ScanNet benchmark's domain: the prediction at a vertex is transfer_labels
 of the saved scene).  With --gt DIR the sites are the cells of the prediction's own lattice, scored against
 DIR/<scene>/{tsdf_info.pkl, full_tsdf_layer0, full_semantic_layer_interpolate0, full_instance_layer_interpolate0}
-(generate_gt's files), so that geometry errors cost IoU.
+(generate_gt's files), so that geometry errors cost IoU.  With --views DATA_PATH the sites are the pixels of every
+--every-th frame of DATA_PATH/<scene> (pose/, intrinsic/): the predicted mesh with its vertex ids and the labelled
+ground-truth mesh --gt_mesh/<scene>_vh_clean_2.ply (labels: --info) are both rendered into those cameras
+(eprecon_amd/render.py), which weighs a surface by how much of the video saw it.
 
 The reference ships no scoring code; the rules (segments, void, the contingency table, matching, the figures) are this
 project's and are written down in DESIGN.md §5b.  What runs on the device is the count of sites per (predicted segment,
@@ -28,7 +33,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .evaluation import _need_device
+from .evaluation import _need_device, read_ply
 from .generate_gt import load_panoptic_points
 from .generate_semantic_instance import SCANNET20_MAPPING, _c_i32, _mapping_list, _query, _scene_volumes, brick_masks
 from .scene_fusion import STUFF_IDS
@@ -406,17 +411,74 @@ def score_voxels(pred_npz, gt_scene_dir, gt_surface=1.0, mapping=SCANNET20_MAPPI
     return tables
 
 
+def score_pixels(pred_npz, gt_mesh_path, info_dir, scene, K, poses, height, width, mapping=SCANNET20_MAPPING, threshold=0.5,
+                 stuff_ids=STUFF_IDS, valid_classes=VALID_CLASSES, device=None, chunk=32, **raster):
+    """The pixel domain: the mesh of the saved scene `pred_npz` with its vertex ids against the mesh `gt_mesh_path`
+    (<scene>_vh_clean_2.ply) labelled at its vertices by <info_dir>/<scene>_{sem_label,ins_label}.npy, both rendered into
+    the cameras K [3,3], poses [V,4,4] at height x width (render.visibility's **raster: znear, zfar, cull_back,
+    pixel_center).  Both vertex sets are ranked once; every pixel takes the rank of the nearest corner of the triangle it
+    sees, -1 where a side shows nothing (no prediction / no ground truth).  The pairs are counted per chunk of views and
+    the tables added on the device; the sites are all pixels of the given frames.  ValueError when the label files and
+    the mesh differ in vertex count.  One host read of its own (the tables)."""
+    from . import render as RD
+    device = torch.device(device if device is not None else "cuda")
+    verts, faces, vsem, vins = RD.scene_mesh(pred_npz, device)
+    gt_verts, gt_faces = read_ply(gt_mesh_path)
+    _, gt_sem, gt_ins = load_panoptic_points(info_dir, scene)
+    if len(gt_sem) != len(gt_verts) or len(gt_ins) != len(gt_verts):
+        raise ValueError(f"{scene}: {len(gt_verts)} vertices in {gt_mesh_path}, {len(gt_sem)} semantic and {len(gt_ins)} instance "
+                         f"labels in {info_dir}")
+    to_dev = lambda a, dtype: torch.from_numpy(np.ascontiguousarray(a).astype(dtype)).to(device)
+    gt_verts, gt_faces = to_dev(gt_verts, np.float32), to_dev(gt_faces, np.int32)
+    p_rank, p_keys, bad = _pred_table(vsem, vins, mapping, stuff_ids, valid_classes)
+    g_rank, _, g_keys, _ = _segment_table(to_dev(gt_sem, np.int64).reshape(-1), to_dev(gt_ins, np.int64).reshape(-1), None,
+                                          stuff_ids, valid_classes, False)
+    poses = np.asarray(poses, np.float64).reshape(-1, 4, 4)
+    pc = raster.get("pixel_center", 0.5)
+    counts, status = _table_buffers(p_keys.numel(), g_keys.numel(), device)
+    counts.zero_()
+    status.zero_()
+    chunk = max(int(chunk), 1)
+    for s in range(0, len(poses), chunk):
+        images = []
+        for v, f, rank in ((verts, faces, p_rank), (gt_verts, gt_faces, g_rank)):
+            vis = RD.visibility(v, f, K, poses[s:s + chunk], height, width, **raster)
+            images.append(RD.resolve(vis, v, f, K, poses[s:s + chunk], labels=(rank,), backgrounds=(-1,), pixel_center=pc,
+                                     outputs=())["labels"][0])
+        c, st = _launch_pair_counts(images[0], images[1], p_keys.numel(), g_keys.numel())
+        counts += c
+        status |= st
+    return _read_tables(counts, status, bad, p_keys, g_keys, threshold, valid_classes, "score_pixels")
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="panoptic quality (PQ, SQ, RQ) and semantic IoU of saved scenes")
     ap.add_argument("--pred", required=True, help="directory of the <scene>.npz files SaveScene wrote")
     ap.add_argument("--scenes", required=True, help="text file, one scene name per line")
-    domain = ap.add_mutually_exclusive_group(required=True)
+    # (--info names the vertex domain on its own and the labels of the pixel domain next to --views, so it cannot sit in
+    # the exclusive group with --views; the rules the group used to state are checked below)
+    domain = ap.add_mutually_exclusive_group()
     domain.add_argument("--gt", help="voxel domain: directory of generate_gt's <scene>/ directories")
-    domain.add_argument("--info", help="vertex domain: directory of <scene>_{vert,sem_label,ins_label}.npy")
+    domain.add_argument("--views", metavar="DATA_PATH", help="pixel domain: ScanNet-layout scenes <scene>/pose, intrinsic; "
+                        "needs --info (the vertex labels) and --gt_mesh")
+    ap.add_argument("--info", help="vertex domain: directory of <scene>_{vert,sem_label,ins_label}.npy")
+    ap.add_argument("--gt_mesh", help="pixel domain: directory of the <scene>_vh_clean_2.ply meshes")
+    ap.add_argument("--every", default=10, type=int, help="pixel domain: every n-th frame (default 10)")
+    ap.add_argument("--size", default=[640, 480], type=int, nargs=2, metavar=("W", "H"), help="pixel domain: image size")
     ap.add_argument("--threshold", default=0.5, type=float, help="a pair matches above this IoU (default 0.5)")
     ap.add_argument("--gt_surface", default=1.0, type=float, help="voxel domain: ground truth is present where |tsdf| is below this")
     ap.add_argument("--out", default=None, help="write the summary as JSON here")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.views is not None:
+        if args.info is None or args.gt_mesh is None:
+            ap.error("--views needs --info and --gt_mesh")
+    elif args.gt is not None and args.info is not None:
+        ap.error("argument --info: not allowed with argument --gt")
+    elif args.gt is None and args.info is None:
+        ap.error("one of the arguments --gt --info --views is required")
+    elif args.gt_mesh is not None:
+        ap.error("--gt_mesh belongs to --views")
+    return args
 
 
 def main(argv=None):
@@ -426,7 +488,12 @@ def main(argv=None):
     score = PanopticScore()
     for scene in scenes:
         npz = os.path.join(args.pred, scene + ".npz")
-        if args.gt is not None:
+        if args.views is not None:
+            from .render import scene_views
+            _, k, poses = scene_views(args.views, scene, args.every, tuple(args.size))
+            score.add(score_pixels(npz, os.path.join(args.gt_mesh, scene + "_vh_clean_2.ply"), args.info, scene, k, poses,
+                                   args.size[1], args.size[0], threshold=args.threshold))
+        elif args.gt is not None:
             score.add(score_voxels(npz, os.path.join(args.gt, scene), gt_surface=args.gt_surface, threshold=args.threshold))
         else:
             score.add(score_vertices(npz, args.info, scene, threshold=args.threshold))

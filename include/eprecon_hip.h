@@ -914,6 +914,38 @@ int eprecon_render_depth_async(const float *verts, int64_t n_verts, const int32_
                                int n_views, int height, int width, float pixel_center, float znear, float zfar, int cull_back,
                                float *depth_out, int64_t queue_capacity, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * View rendering  (csrc/mesh_render.hip; tools/render.py and VIS_INCREMENTAL of the reference open a pyrender window)
+ *
+ * Visibility buffer  (the depth rasteriser's walk, setup, coverage and depth: csrc/mesh_raster.hpp)
+ *   verts, faces, cams, pixel_center, znear, zfar, cull_back, queue_capacity: as eprecon_render_depth_async.
+ *   vis_out u64[n_views,h,w]: (fp32 depth bits << 32) | face index of the nearest drawn face, lowered by a 64-bit
+ *   atomicMin from all-ones; "no hit" is an upper word at or above the +inf bits 0x7F800000.  Run-to-run
+ *   bit-identical; the upper word equals the depth render's z-buffer bit for bit; at equal depth bits the smallest
+ *   face index wins.  Four fixed launches; workspace: eprecon_render_visibility_workspace_bytes(queue_capacity).
+ *
+ * Resolve  (one thread per pixel; every output is optional: a null pointer skips it)
+ *   The winning face is rebuilt in the camera frame and its corners weighed by the ray's triple products
+ *   w_a : w_b : w_c = d.(b x c) : d.(c x a) : d.(a x b); "the corner" is the one with the largest |w| (the earlier
+ *   slot of the face on ties).  depth_out f32 (0 where nothing is hit), face_out int32 (-1), corner_out int32: that
+ *   corner's vertex index (-1), label_a_out / label_b_out int32: labels_a / labels_b int32[nv] at that corner
+ *   (background_a / background_b), rgb_out u8[n_views,h,w,3]: min(255, floor(c I + 0.5)) with
+ *   I = ambient + (1 - ambient) |n^ . d^| (unit face normal, unit pixel ray, fp64) and c the corner's colour in
+ *   colors u8[nv,3] (153 when colors is null); (bg_red, bg_green, bg_blue) where nothing is hit.  A word of vis whose face
+ *   index is not a drawable face of this mesh counts as no hit.  One launch.
+ * ------------------------------------------------------------------------------------------ */
+size_t eprecon_render_visibility_workspace_bytes(int64_t queue_capacity);
+int eprecon_render_visibility_async(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const double *cams,
+                                    int n_views, int height, int width, float pixel_center, float znear, float zfar,
+                                    int cull_back, uint64_t *vis_out, int64_t queue_capacity, void *workspace,
+                                    size_t workspace_bytes, void *stream);
+int eprecon_render_resolve_async(const uint64_t *vis, const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces,
+                                 const double *cams, int n_views, int height, int width, float pixel_center, float *depth_out,
+                                 int32_t *face_out, int32_t *corner_out, const int32_t *labels_a, int32_t background_a,
+                                 int32_t *label_a_out, const int32_t *labels_b, int32_t background_b, int32_t *label_b_out,
+                                 const uint8_t *colors, double ambient, int bg_red, int bg_green, int bg_blue,
+                                 uint8_t *rgb_out, void *stream);
+
 /* Depth metrics (eval_depth of tools/evaluation_utils.py, batched): pred, trgt f32[n_frames, n_pix].  sums_out
  * f64[n_frames, 10] per frame, in a fixed order (run-to-run bit-identical): valid pixels (pred > 0, 0 < trgt < 10),
  * pixels with pred > 0, then over the valid pixels sum |p-t|/t, |p-t|, (p-t)^2/t, (p-t)^2, (ln p - ln t)^2 and the
