@@ -201,7 +201,13 @@ SIGNATURES = {
     "eprecon_conv_pack_many_async": (_i, [_vp, _i, _vp]),
     "eprecon_nchw_to_nhwc_async": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "eprecon_views_to_rows_async": (_i, [_vp, _vp]),
+    "eprecon_prepare_views_async": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "eprecon_depth_to_metres_async": (_i, [_vp, _i64, _f, _vp, _vp]),
 }
+
+# include/eprecon_hip.h: EPRECON_VIEWS_TILE_H (the output rows a workgroup of eprecon_prepare_views_async owns: the caller sizes
+# the LDS window from it) and EPRECON_VIEWS_MAX_KSIZE
+VIEWS_TILE_H, VIEWS_MAX_KSIZE = 16, 9
 
 EPRECON_OK, EPRECON_EMPTY = 0, 1
 ABI_VERSION = 1

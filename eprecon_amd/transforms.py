@@ -14,6 +14,9 @@ torch CPU operations, split into functions; the occupancy targets come from TSDF
 target from ONE eprecon_gt_crop_async launch (csrc/gt_crop.hip).  A scene's full volumes live on the device in a
 `SceneVolumes`, instead of being converted to float tensors for every sample; the reference's lists are accepted too.
 
+`PrepareViews` stands for the reference's ResizeImage + ToTensor where the frames come decoded from disk (scannet.py): the
+resize, the float conversion and the re-layout run in one launch of csrc/prepare_views.hip, bit-identical to PIL's.
+
 `IntrinsicsPoseToProjection.world_to_aligned_camera` is a RESTATEMENT: the reference builds the rotation with transforms3d
 (axis-angle -> quaternion -> matrix), which is not available to this project; synthetic.world_to_aligned_camera builds the
 same rotation with Rodrigues' formula.
@@ -164,13 +167,31 @@ class IntrinsicsPoseToProjection:
         return f"IntrinsicsPoseToProjection(n_views={self.nviews}, stride={self.stride})"
 
 
+def frame_padding(image_wh):
+    """black rows above (and as many below) a frame of image_wh = (width, height) before it is resized"""
+    return 2 if tuple(image_wh) == (1296, 968) else 0
+
+
+def fit_intrinsics(k, image_wh, size):
+    """The intrinsics `k` (3x3, for an image of image_wh = (width, height)) follow the image to `size` = (width, height), in
+    place.  A 1296 x 968 ScanNet colour frame is first centred between 2 + 2 black rows, which makes it 4:3 like the target;
+    the principal point moves down with it.  Returns that padding in rows (0 for every other size)."""
+    w, h = image_wh
+    pad = frame_padding(image_wh)
+    if pad:
+        h += 2 * pad
+        k[1, 2] += pad
+    k[0, :] /= w / size[0]
+    k[1, :] /= h / size[1]
+    return pad
+
+
 def _resize_image_class():
     from PIL import Image
 
     class ResizeImage:
         """PIL images of a sample -> float32 arrays of `size` = (width, height), bilinear, with the intrinsics (given for the
-        images as they come) following.  A 1296 x 968 ScanNet colour frame is first centred on a black 1296 x 972 canvas,
-        which makes it 4:3 like the target; the principal point moves down with it."""
+        images as they come) following (fit_intrinsics, which also says when a frame is padded first)."""
 
         def __init__(self, size):
             self.size = tuple(size)
@@ -179,14 +200,11 @@ def _resize_image_class():
             new_w, new_h = self.size
             for v, img in enumerate(data["imgs"]):
                 k = data["intrinsics"][v]
-                if img.size == (1296, 968):
-                    canvas = Image.new(img.mode, (1296, 972))
-                    canvas.paste(img, (0, 2))
+                pad = fit_intrinsics(k, img.size, self.size)
+                if pad:
+                    canvas = Image.new(img.mode, (img.size[0], img.size[1] + 2 * pad))
+                    canvas.paste(img, (0, pad))
                     img = canvas
-                    k[1, 2] += 2
-                w, h = img.size
-                k[0, :] /= w / new_w
-                k[1, :] /= h / new_h
                 data["imgs"][v] = np.asarray(img.resize((new_w, new_h), Image.BILINEAR), dtype=np.float32)
                 data["intrinsics"][v] = k
             return data
@@ -207,6 +225,184 @@ def __getattr__(name):
         globals()[name] = cls
         return cls
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+# ---------------------------------------------------------------- view preparation on the device (csrc/prepare_views.hip)
+MAX_RESAMPLE_SCALE = 4      # per axis: 2 * ceil(4) + 1 = _lib.VIEWS_MAX_KSIZE taps
+_RESAMPLE_BITS = 22
+
+
+def resample_table(n_in, n_out):
+    """int32[n_out, 2 + ksize]: per output index of one axis the first tap, the number of taps and their coefficients with
+    22 fractional bits — PIL's 8-bit bilinear resampling of n_in samples to n_out (include/eprecon_hip.h states the
+    arithmetic), float64 on the host.  The identity's rows are (xx, 2 | 1, 0): no special case anywhere."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"cannot resample {n_in} samples to {n_out}")
+    scale = n_in / n_out
+    if scale > MAX_RESAMPLE_SCALE:
+        raise ValueError(f"{n_in} -> {n_out} shrinks by {scale:.3f}, more than the {MAX_RESAMPLE_SCALE} view preparation accepts")
+    fs = max(scale, 1.0)
+    ksize = 2 * int(np.ceil(fs)) + 1
+    centre = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    first = np.maximum(np.trunc(centre - fs + 0.5), 0)
+    taps = np.minimum(np.trunc(centre + fs + 0.5), n_in) - first
+    x = np.arange(ksize, dtype=np.float64)[None, :]
+    w = np.maximum(0.0, 1.0 - np.abs((x + first[:, None] - centre[:, None] + 0.5) / fs))
+    w[x >= taps[:, None]] = 0.0
+    total = np.zeros(n_out)
+    for j in range(ksize):                  # the sum in index order
+        total += w[:, j]
+    table = np.empty((n_out, 2 + ksize), np.int32)
+    table[:, 0], table[:, 1] = first, taps
+    table[:, 2:] = np.trunc(0.5 + w / total[:, None] * (1 << _RESAMPLE_BITS))
+    return table
+
+
+def _window_rows(table, tile):
+    """the most source rows a tile of `tile` consecutive outputs reaches: what a workgroup keeps in LDS"""
+    first, end = table[:, 0].astype(np.int64), table[:, 0].astype(np.int64) + table[:, 1]
+    starts = np.arange(0, len(table), tile)
+    return int((end[np.minimum(starts + tile, len(table)) - 1] - first[starts]).max())
+
+
+_TABLES = {}
+
+
+def _device_table(n_in, n_out, device):
+    """(table on the device, ksize, host table), built once per (n_in, n_out, device)"""
+    key = (int(n_in), int(n_out), device.type, device.index)
+    hit = _TABLES.get(key)
+    if hit is None:
+        host = resample_table(n_in, n_out)
+        hit = _TABLES[key] = (torch.from_numpy(host).to(device), host.shape[1] - 2, host)
+    return hit
+
+
+def prepare_views(frames, size, pad_top=0, pad_bottom=0, out=None):
+    """frames: uint8[V,H,W,3] device tensor -> f32[V,3,h,w] for `size` = (w, h): every frame, standing between pad_top and
+    pad_bottom black rows, resized as PIL's resize(size, BILINEAR) does it and converted to float.  One launch."""
+    if not (torch.is_tensor(frames) and frames.is_cuda):
+        raise _lib.EpreconError("prepare_views needs a GPU tensor (no CPU fallback)")
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise ValueError(f"frames are contiguous uint8[V,H,W,3], got {frames.dtype} {tuple(frames.shape)}")
+    n_views, height, width = (int(s) for s in frames.shape[:3])
+    out_w, out_h = int(size[0]), int(size[1])
+    table_x, ksize_x, _ = _device_table(width, out_w, frames.device)
+    table_y, ksize_y, host_y = _device_table(pad_top + height + pad_bottom, out_h, frames.device)
+    if out is None:
+        out = torch.empty((n_views, 3, out_h, out_w), dtype=torch.float32, device=frames.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n_views, 3, out_h, out_w) or not out.is_contiguous():
+        raise ValueError(f"out is contiguous f32{(n_views, 3, out_h, out_w)}")
+    with torch.cuda.device(frames.device):
+        _lib.check(_lib.load().eprecon_prepare_views_async(
+            _lib.ptr(frames), n_views, height, width, int(pad_top), int(pad_bottom), _lib.ptr(table_x), ksize_x,
+            _lib.ptr(table_y), ksize_y, _window_rows(host_y, _lib.VIEWS_TILE_H), out_h, out_w, _lib.ptr(out),
+            _lib.current_stream()), "eprecon_prepare_views_async")
+    return out
+
+
+def depth_to_metres(depth_mm, max_depth=3.0):
+    """depth_mm: 16-bit device tensor of any shape holding uint16 millimetres (torch.uint16, or the same bits as int16) ->
+    f32 metres of that shape, d / 1000 and 0 beyond max_depth (datasets/scannet.py:57-63)"""
+    if not (torch.is_tensor(depth_mm) and depth_mm.is_cuda):
+        raise _lib.EpreconError("depth_to_metres needs a GPU tensor (no CPU fallback)")
+    if depth_mm.element_size() != 2 or depth_mm.is_floating_point() or not depth_mm.is_contiguous():
+        raise ValueError(f"depth is a contiguous 16-bit integer tensor, got {depth_mm.dtype}")
+    out = torch.empty(depth_mm.shape, dtype=torch.float32, device=depth_mm.device)
+    with torch.cuda.device(depth_mm.device):
+        _lib.check(_lib.load().eprecon_depth_to_metres_async(_lib.ptr(depth_mm), depth_mm.numel(), float(max_depth),
+                                                             _lib.ptr(out), _lib.current_stream()),
+                   "eprecon_depth_to_metres_async")
+    return out
+
+
+class PrepareViews:
+    """Stands where the reference has ResizeImage followed by ToTensor, with the resize, the float conversion and the
+    re-layout on the device: 'imgs' (PIL images or uint8[H,W,3] arrays, as decoded) become f32[V,3,h,w] there, bit for bit
+    what the two host stages make; 'intrinsics' follow by fit_intrinsics; 'depth' given as uint16 millimetres becomes f32
+    metres on the device (float depth goes the host way, as in ToTensor).  The frames (and the depth) of a sample cross in
+    ONE copy from a reused pinned buffer; views of different sizes are resized group by group, one launch per size."""
+
+    def __init__(self, size=(640, 480), max_depth=3.0, device=None):
+        self.size = (int(size[0]), int(size[1]))
+        self.max_depth = max_depth
+        self.device = torch.device(device) if device is not None else torch.device("cuda")
+        if self.device.type != "cuda":
+            raise _lib.EpreconError("PrepareViews needs a GPU (no CPU fallback)")
+        self._pinned = None
+        self._copied = None      # event behind the last copy out of the pinned buffer
+
+    def _stage(self, nbytes):
+        """the pinned buffer as a numpy byte array of at least nbytes, free to be written (the last copy has left it)"""
+        if self._copied is not None:
+            self._copied.synchronize()
+        if self._pinned is None or self._pinned.numel() < nbytes:
+            self._pinned = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        return self._pinned.numpy()
+
+    def __call__(self, data):
+        frames = [np.asarray(img) for img in data["imgs"]]
+        for f in frames:
+            if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
+                raise ValueError(f"a colour frame is uint8[H,W,3] (or an RGB PIL image), got {f.dtype} {f.shape}")
+        groups = {}                       # (H, W) -> the views of that size, in order
+        for v, f in enumerate(frames):
+            groups.setdefault(f.shape[:2], []).append(v)
+        for shape in groups:              # refuse a size before anything is copied
+            for n_in, n_out in ((shape[1], self.size[0]), (shape[0] + 2 * frame_padding(shape[::-1]), self.size[1])):
+                if n_in > MAX_RESAMPLE_SCALE * n_out:
+                    raise ValueError(f"a {shape[1]} x {shape[0]} frame shrinks by more than {MAX_RESAMPLE_SCALE} to {self.size}")
+        depth = data.get("depth")
+        raw_depth = depth is not None and all(isinstance(d, np.ndarray) and d.dtype == np.uint16 for d in depth)
+        if raw_depth:
+            depth = np.stack(depth)
+        align = lambda n: (n + 255) // 256 * 256
+        offsets, total = {}, 0
+        for shape, views in groups.items():
+            offsets[shape] = total
+            total = align(total + len(views) * shape[0] * shape[1] * 3)
+        depth_offset = total
+        if raw_depth:
+            total += depth.nbytes
+        host = self._stage(total)
+        for shape, views in groups.items():
+            dst = host[offsets[shape]:offsets[shape] + len(views) * shape[0] * shape[1] * 3].reshape((len(views),) + shape + (3,))
+            for j, v in enumerate(views):
+                dst[j] = frames[v]
+        if raw_depth:
+            host[depth_offset:total] = depth.reshape(-1).view(np.uint8)
+        with torch.cuda.device(self.device):
+            staged = torch.empty(total, dtype=torch.uint8, device=self.device)
+            staged.copy_(self._pinned[:total], non_blocking=True)
+            if self._copied is None:
+                self._copied = torch.cuda.Event()
+            self._copied.record()
+            n_views, (out_w, out_h) = len(frames), self.size
+            imgs = torch.empty((n_views, 3, out_h, out_w), dtype=torch.float32, device=self.device)
+            for shape, views in groups.items():
+                src = staged[offsets[shape]:offsets[shape] + len(views) * shape[0] * shape[1] * 3].view((len(views),) + shape + (3,))
+                pads = [fit_intrinsics(data["intrinsics"][v], (shape[1], shape[0]), self.size) for v in views]
+                if len(groups) == 1:
+                    prepare_views(src, self.size, pads[0], pads[0], out=imgs)
+                else:
+                    imgs[torch.as_tensor(views, device=self.device)] = prepare_views(src, self.size, pads[0], pads[0])
+            data["imgs"] = imgs
+            if raw_depth:
+                mm = staged[depth_offset:total].view(torch.int16).view(depth.shape)
+                data["depth"] = depth_to_metres(mm, self.max_depth)
+        for key in ("intrinsics", "extrinsics"):
+            data[key] = _float_tensor(data[key])
+        if depth is not None and not raw_depth:
+            data["depth"] = _float_tensor(np.stack(depth))
+        if not isinstance(data.get("tsdf_list_full"), SceneVolumes):
+            for key in FULL_VOLUME_KEYS:
+                if key in data:
+                    data[key] = [_float_tensor(v) for v in data[key]]
+        return data
+
+    def __repr__(self):
+        return f"PrepareViews(size={self.size}, max_depth={self.max_depth})"
 
 
 # ---------------------------------------------------------------- host side: float32 torch CPU operations, pinned by the golden

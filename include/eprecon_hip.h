@@ -1336,6 +1336,37 @@ int eprecon_back_project_backward_det_async(const int32_t *coords_valid, int64_t
                                             const float *dmean, float *dfeats_nhwc, void *workspace, size_t workspace_bytes,
                                             void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * View preparation  (csrc/prepare_views.hip: what the data loader does to a fragment's frames before the network sees
+ * them — datasets/transforms.py ResizeImage + ToTensor, datasets/scannet.py:57-63 — in one launch each)
+ *
+ * eprecon_prepare_views_async: frames uint8[n_views, height, width, 3] (decoded RGB) -> out f32[n_views, 3, out_h, out_w],
+ *   every element the 8-bit bilinear resize of the frame standing between pad_top and pad_bottom black rows (which are
+ *   never materialised), as a float.  The arithmetic is two integer passes, horizontal first, each
+ *       clamp((2^21 + sum_x pixel[xmin + x] * k[x]) >> 22, 0, 255)   stored as uint8,
+ *   over the taps a table names.  table_x int32[out_w][2 + ksize_x] and table_y int32[out_h][2 + ksize_y] (DEVICE memory,
+ *   built once per (in, out) pair on the host) hold per output index: xmin, n (<= ksize), then ksize coefficients (22
+ *   fractional bits, the unused ones 0); xmin and xmin + n must not decrease along a table.  table_y indexes the padded
+ *   rows 0 .. pad_top + height + pad_bottom.
+ *   A workgroup owns EPRECON_VIEWS_TILE_W x EPRECON_VIEWS_TILE_H output pixels of one view and keeps the horizontally
+ *   resampled source rows of its vertical window in LDS: lds_rows = the largest such window over the row tiles of table_y
+ *   (rows ymin of the tile's first output row .. ymin + n of its last), computed by the caller from the table it built.
+ *   A tap the tables name outside the frame, or outside the LDS window, is skipped (never read): wrong tables give wrong
+ *   values, not wild accesses.
+ *   EPRECON_ERR_ARG: a NULL pointer, a size <= 0, a negative padding, ksize outside 1..EPRECON_VIEWS_MAX_KSIZE;
+ *   EPRECON_ERR_UNSUPPORTED: an LDS window beyond what a workgroup may ask for, more than 2^31 - 1 source bytes or outputs.
+ *
+ * eprecon_depth_to_metres_async: depth_mm uint16[n] -> out f32[n] = (float)d / 1000.0f (IEEE division), 0 where that
+ *   exceeds max_depth.
+ * ------------------------------------------------------------------------------------------ */
+#define EPRECON_VIEWS_TILE_W 64
+#define EPRECON_VIEWS_TILE_H 16
+#define EPRECON_VIEWS_MAX_KSIZE 9      /* scale <= 4 per axis: 2 * ceil(4) + 1 */
+int eprecon_prepare_views_async(const uint8_t *frames, int n_views, int height, int width, int pad_top, int pad_bottom,
+                                const int32_t *table_x, int ksize_x, const int32_t *table_y, int ksize_y, int lds_rows,
+                                int out_h, int out_w, float *out, void *stream);
+int eprecon_depth_to_metres_async(const uint16_t *depth_mm, int64_t n, float max_depth, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
