@@ -233,13 +233,13 @@ def calibrate_occupancy_heads(net, features, features_occ_pano=None, inputs=None
         _calibrate(net, frags, keep_fraction)
     finally:
         _NN.WARN_TAG = old_tag
-        net.gru_fusion.scene_name = [None, None, None]
+        net.gru_fusion.new_scene()
         net.trace = old_trace
 
 
 def _calibrate(net, frags, keep_fraction):
     for i in range(net.cfg.N_LAYER):
-        net.gru_fusion.scene_name = [None, None, None]
+        net.gru_fusion.new_scene()
         occs = []
         for k, (f1, f2, inp) in enumerate(frags):
             net.trace = []
@@ -332,7 +332,7 @@ class Cfg4Step:
     @torch.no_grad()
     def run(self):
         if self.k == 0:
-            self.net.gru_fusion.scene_name = [None, None, None]
+            self.net.gru_fusion.new_scene()
         f1, f2, inp = self.frags[self.k]
         seed_subsampling(self.k)
         self.last, _ = self.net(f1, f2, inp, {})
@@ -363,13 +363,13 @@ class Cfg4Step:
         self.flush()
         dec, self.net.panoptic = self.net.panoptic, None
         try:
-            self.net.gru_fusion.scene_name = [None, None, None]
+            self.net.gru_fusion.new_scene()
             f1, f2, inp = self.frags[0]
             seed_subsampling(0)
             out, _ = self.net(f1, f2, inp, {})
         finally:
             self.net.panoptic = dec
-            self.net.gru_fusion.scene_name = [None, None, None]
+            self.net.gru_fusion.new_scene()
             self.k = 0
         if "coords" not in out:
             raise RuntimeError("cfg3: NeuConNet.forward returned before the finest level")
@@ -421,7 +421,7 @@ class E2EStep:
     @torch.no_grad()
     def run(self):
         if self.k == 0:   # scene restart: both persistent maps (GRU features, fused TSDF / instances)
-            self.model.neucon_net.gru_fusion.scene_name = [None, None, None]
+            self.model.neucon_net.gru_fusion.new_scene()
             self.model.fuse_to_global.scene_name = [None, None, None]
         seed_subsampling(self.k)
         self.last, _ = self.model(self.inputs[self.k], save_mesh=False, training=False)
@@ -496,7 +496,7 @@ class TrainStep:
                 "parallelism": "DistributedDataParallel over RCCL, one fragment per rank" if self.model is not self.net else "single"}
 
     def loss(self):
-        self.net.gru_fusion.scene_name = [None, None, None]
+        self.net.gru_fusion.new_scene()
         seed_subsampling(0)
         outputs, loss_dict = self.model(self.f1, self.f2, self.inputs, {})
         total = 0

@@ -31,22 +31,13 @@ def _queue_select(logit, coords, batch_size, dim, cell, threshold, dense):
     return out, counts
 
 
-def init_select(logit, coords, batch_size, dim=24, cell=4, threshold=0.3, must_be_zero=(), dense=None):
+def init_select(logit, coords, batch_size, dim=24, cell=4, threshold=0.3, dense=None):
     """models/neucon_network.py:264,298-318.  logit f32[N(,1)] and coords int32[N,4] of the valid
     48^3 voxels -> int32[M,4] stage-0 coordinates (raster order per batch element) and the
     per-batch counts (one host sync, like the reference's torch.nonzero).
-    must_be_zero: int32 device scalars ([1]-shaped) read back in the SAME host read; a non-zero one raises (the
-    off-grid counters of the dense-grid convolution maps that produced `logit`, sparse.DenseMap).
     dense: the DenseMap of the voxel set when it has one (one batch element): marks through its rank volume, no clear."""
     out, counts = _queue_select(logit, coords, batch_size, dim, cell, threshold, dense)
-    if must_be_zero:
-        host = _lib.read_counts(torch.cat([counts] + [t.reshape(1) for t in must_be_zero]))
-        if any(host[1 + batch_size:]):
-            raise _lib.EpreconError(f"dense-grid convolution: {host[1 + batch_size:]} voxels of the set are not on the grid "
-                                    "their VoxelSet was declared with (rows left unwritten); EPRECON_ERR_ARG")
-        host = host[:1 + batch_size]
-    else:
-        host = _lib.read_counts(counts)     # (the off-grid counters of dense-grid maps ride along: sparse.DenseMap defers them)
+    host = _lib.read_counts(counts)     # (the off-grid counters of dense-grid maps ride along: sparse.DenseMap defers them)
     return out[: host[0]], host[1:]
 
 

@@ -14,6 +14,8 @@ models/neucon_network.py:488).  One fragment step (per batch element):
 `direct_substitute=True` (scene-level TSDF substitution + instance association, a15) dispatches to
 eprecon_amd/scene_fusion.py.
 """
+import os
+
 import torch
 import torch.nn as nn
 
@@ -79,7 +81,6 @@ class GRUFusion(nn.Module):
             self._scene = SceneFusion(cfg)
             return
         self.ch_in = list(ch_in)
-        self.feat_init = 0
         self.ch_voxel = list(ch_voxel)
         self.ch_img = [a - b for a, b in zip(ch_in, ch_voxel)]
         self.n_scales = len(cfg.THRESHOLDS) - 1
@@ -97,15 +98,19 @@ class GRUFusion(nn.Module):
             self.fusion_nets_img.append(ConvGRU(hidden_dim=ch, input_dim=ch, pres=1,
                                                 vres=cfg.VOXEL_SIZE * 2 ** (self.n_scales - i)))
         self._identity_fusion = False  # tests: skip the ConvGRUs (pins the bookkeeping alone)
-        self.two_streams = __import__("os").environ.get("EPRECON_GRU_STREAMS", "1") == "1"
+        self.two_streams = os.environ.get("EPRECON_GRU_STREAMS", "1") == "1"
         # EPRECON_GRU_STAGE=0: the level's bookkeeping as separate calls with a host read each (crop_union, target_fuse, the
         # two unique-voxel counts) instead of ONE queued stage call + one read (GlobalMap.stage_begin)
-        self.stage_call = __import__("os").environ.get("EPRECON_GRU_STAGE", "1") == "1"
+        self.stage_call = os.environ.get("EPRECON_GRU_STAGE", "1") == "1"
         self._side = None
         self._xchg = None              # multi-GPU: distributed.BoundaryExchange (stamps of the map voxels)
         self._n_exchanged = self._cur_fragment = 0
         self._xchg_stream = None       # the exchange's own stream: its one host read must not drain the main stream
         self._map_ready = None         # event behind the last map update (what the exchange has to wait for)
+
+    def new_scene(self):
+        """the next fragment starts a new scene at every scale: _begin_fragment then empties the maps and takes its origin"""
+        self.scene_name = [None, None, None]
 
     def reset(self, i, device=None):
         """models/gru_fusion.py:59-65: empty maps (the handles keep their device memory)"""
@@ -170,7 +175,7 @@ class GRUFusion(nn.Module):
         n = self.cfg.N_LAYER
         if self._xchg is None:
             self._xchg = D.BoundaryExchange(n, dev)
-        if dev.type == "cuda" and __import__("os").environ.get("EPRECON_XCHG_STREAM", "1") == "1":
+        if os.environ.get("EPRECON_XCHG_STREAM", "1") == "1":
             # The exchange reads the maps as the PREVIOUS fragment's last update left them and needs one host read (the
             # counts).  On the main stream that read would wait for everything queued there — the host runs milliseconds
             # ahead of the GPU — and end the run-ahead at the start of every fragment.  On its own stream it waits only for
@@ -200,68 +205,138 @@ class GRUFusion(nn.Module):
         # global index of the fragment this rank fuses next: ranks take the fragments of a scene round-robin
         self._cur_fragment = self._n_exchanged * dist.get_world_size() + dist.get_rank()
         self._n_exchanged += 1
-        if dev.type == "cuda":
-            # selection / packing / merge as kernels on the map handles; the stamps are a column of the map
-            self._xchg.exchange_handles([self.global_volume[scale] for scale in range(n)], rels, dims)
-            for scale in range(n):
-                self.global_volume[scale].set_fragment(self._cur_fragment)
+        # selection / packing / merge as kernels on the map handles; the stamps are a column of the map
+        self._xchg.exchange_handles([self.global_volume[scale] for scale in range(n)], rels, dims)
+        for scale in range(n):
+            self.global_volume[scale].set_fragment(self._cur_fragment)
+
+    def _convgru_pair(self, scale, hx_v, hx_i, r_coords, values, prepare=False):
+        """the two cells of a level on their [h | x] buffers -> values[:, :chv], values[:, chv:].  Both see the same points: their
+        six SConv3d share two voxelisations (torchsparse_utils), built first when the caller registered them (`prepare`) or the
+        cells run on two HIP streams (independent channel groups, each a chain of small kernels that leaves most CUs idle alone)."""
+        chv = self.ch_voxel[scale]
+        chi = self.ch_in[scale] - chv
+        gv, gi = self.fusion_nets_voxel[scale], self.fusion_nets_img[scale]
+        two = self.two_streams and not torch.is_grad_enabled()
+        if two or prepare:
+            prepare_convgru_voxelizations(r_coords, gv.convz.pres, gv.convz.vres)   # kernel maps, point lists, corner tables
+        run_v = lambda: gv(PointTensor(hx_v[:, :chv], r_coords), PointTensor(hx_v[:, chv:], r_coords), out=values[:, :chv])
+        run_i = lambda: gi(PointTensor(hx_i[:, :chi], r_coords), PointTensor(hx_i[:, chi:], r_coords), out=values[:, chv:])
+        if not two:
+            run_v()
+            run_i()
             return
-        maps = [self.global_volume[scale].export() for scale in range(n)]
-        for scale, (c, f) in enumerate(self._xchg.exchange(maps, rels, dims)):
-            if c.shape[0] != maps[scale][0].shape[0] or f is not maps[scale][1]:
-                self.global_volume[scale].set(c, f)
+        main = torch.cuda.current_stream(values.device)
+        if self._side is None:
+            self._side = _lib.side_stream(values.device, _lib.SIDE_PAIR)
+        self._side.wait_stream(main)
+        with torch.cuda.stream(self._side):
+            run_i()
+        run_v()
+        main.wait_stream(self._side)
+
+    def _aligned_coords(self, updated, interval, origin, inputs, i):
+        """the union's voxels in the aligned camera frame -> (pts_c int32[N,4] finest units, batch column 0; r_coords)"""
+        pts_c = torch.cat([torch.zeros_like(updated[:, :1]), updated * interval], dim=1)
+        return pts_c, aligned_camera_coords(pts_c, origin.reshape(1, 3), self.cfg.VOXEL_SIZE,
+                                            inputs["world_to_aligned_camera"][i].reshape(1, 4, 4))
+
+    def _fuse_targets(self, scale, i, dim, rel_l, updated, inputs):
+        """the ground-truth twin of the map on its own call -> (tsdf_target, occ_target) | (None, None)"""
+        if "occ_list" not in inputs:
+            return None, None
+        lvl = self.cfg.N_LAYER - scale - 1
+        tsdf_target = self.target_tsdf_volume[scale].target_fuse(inputs["tsdf_list"][lvl][i], inputs["occ_list"][lvl][i], dim,
+                                                                 rel_l, updated)
+        return tsdf_target, tsdf_target.abs() < 1
+
+    def _update_map(self, scale, updated, values, dev):
+        """update_map (:195-215)"""
+        self.global_volume[scale].update(updated, values)
+        if self._xchg is not None:
+            self._map_ready = torch.cuda.current_stream(dev).record_event()
+
+    @staticmethod
+    def _out_coords(i, updated, interval, pts_c):
+        """(batch element 0: the rows the aligned-camera transform was given are these coordinates already)"""
+        return pts_c if i == 0 and pts_c is not None else torch.cat([torch.full_like(updated[:, :1], i), updated * interval], dim=1)
 
     def _fuse_staged(self, scale, i, cur_c, cur_f, dim, interval, rel_l, origin, inputs, dev):
-        """one batch element of one level on the stage call (inference on the GPU): -> (coords, fused values, tsdf_target,
-        occ_target).  One host read for the whole bookkeeping; the ConvGRUs find their voxelisations in the cache."""
-        cfg = self.cfg
-        gmap = self.global_volume[scale]
+        """one batch element of one level -> (coords, fused values, tsdf_target, occ_target), like the two below.  Inference on the
+        stage call: one host read for the whole bookkeeping; the ConvGRUs find their voxelisations in the cache"""
+        cfg, gv = self.cfg, self.fusion_nets_voxel[scale]
         chv, cin = self.ch_voxel[scale], self.ch_in[scale]
         chi = cin - chv
-        gv, gi = self.fusion_nets_voxel[scale], self.fusion_nets_img[scale]
         res = convgru_resolution(gv.convz.pres, gv.convz.vres)
         tmap = tsdf_gt = occ_gt = None
         if "occ_list" in inputs:
             lvl = cfg.N_LAYER - scale - 1
             tmap, tsdf_gt, occ_gt = self.target_tsdf_volume[scale], inputs["tsdf_list"][lvl][i], inputs["occ_list"][lvl][i]
-        st = gmap.stage_begin(tmap, cur_c, cur_f, dim, interval, rel_l, tsdf_gt, occ_gt, origin,
-                              inputs["world_to_aligned_camera"][i], cfg.VOXEL_SIZE, res, chv, batch_index=i).read()
-        n_u = st.n
-        r_coords = st.r_coords
-        if self._identity_fusion:      # tests: the bookkeeping alone
-            e1 = register_voxelization(r_coords, res, st.scaled1, st.vox1, st.inverse1, st.uniq1, st.grid1)
-            register_voxelization(e1.scaled, res, st.scaled2, st.vox2, st.inverse2, st.uniq2, st.grid2)
+        st = self.global_volume[scale].stage_begin(tmap, cur_c, cur_f, dim, interval, rel_l, tsdf_gt, occ_gt, origin,
+                                                   inputs["world_to_aligned_camera"][i], cfg.VOXEL_SIZE, res, chv,
+                                                   batch_index=i).read()
+        first = (st.scaled1, st.vox1, st.inverse1, st.uniq1, st.grid1)
+        second = (st.scaled2, st.vox2, st.inverse2, st.uniq2, st.grid2)
+        values = torch.empty((st.n, cin), dtype=torch.float32, device=dev)
+        if self._identity_fusion:      # tests: the bookkeeping alone (the fragment's rows pass through)
+            e1 = register_voxelization(st.r_coords, res, *first)
+            register_voxelization(e1.scaled, res, *second)
+            values[:, :chv], values[:, chv:] = st.hx_v[:, chv:], st.hx_i[:, chi:]
         else:
             # point lists, kernel maps, corner tables (and the reference's hash order / stale indices) of both voxelisations:
-            # one library call; prepare_convgru_voxelizations below then finds everything in place
-            register_voxelization_pair(r_coords, res, (st.scaled1, st.vox1, st.inverse1, st.uniq1, st.grid1),
-                                       (st.scaled2, st.vox2, st.inverse2, st.uniq2, st.grid2))
+            # one library call; the pair's prepare_convgru_voxelizations then finds everything in place
+            register_voxelization_pair(st.r_coords, res, first, second)
+            self._convgru_pair(scale, st.hx_v, st.hx_i, st.r_coords, values, prepare=True)
+        self._update_map(scale, st.updated, values, dev)
+        return st.out_coords, values, st.tsdf_target, (st.tsdf_target.abs() < 1 if st.tsdf_target is not None else None)
+
+    def _fuse_separate(self, scale, i, cur_c, cur_f, dim, interval, rel_l, origin, inputs, dev):
+        """inference on separate calls with a host read each (crop_union, target_fuse, the two unique-voxel counts)"""
+        gmap = self.global_volume[scale]
+        chv, cin = self.ch_voxel[scale], self.ch_in[scale]
+        chi = cin - chv
+        updated, src_cur, src_glob, _ = gmap.crop_union(cur_c, cur_f, dim, interval, rel_l)
+        n_u = updated.shape[0]
+        # current / global rows gathered straight into the [h | x] buffers of the two ConvGRUs (voxel channels and image
+        # channels): h = the map's row, x = the fragment's row; no concat / slice copies
+        hx_v = torch.empty((n_u, 2 * chv), dtype=torch.float32, device=dev)
+        hx_i = torch.empty((n_u, 2 * chi), dtype=torch.float32, device=dev)
+        gmap.gather(src_glob, 0, chv, hx_v[:, :chv])
+        gmap.gather(src_glob, chv, chi, hx_i[:, :chi])
+        gather_rows(cur_f[:, :chv], src_cur, chv, out=hx_v[:, chv:])
+        gather_rows(cur_f[:, chv:], src_cur, chi, out=hx_i[:, chi:])
+        tsdf_target, occ_target = self._fuse_targets(scale, i, dim, rel_l, updated, inputs)
         values = torch.empty((n_u, cin), dtype=torch.float32, device=dev)
-        hx_v, hx_i = st.hx_v, st.hx_i
-        if self._identity_fusion:          # tests: the bookkeeping alone (the fragment's rows pass through)
+        pts_c = None
+        if self._identity_fusion:      # tests: the bookkeeping alone (the fragment's rows pass through)
             values[:, :chv], values[:, chv:] = hx_v[:, chv:], hx_i[:, chi:]
         else:
-            prepare_convgru_voxelizations(r_coords, gv.convz.pres, gv.convz.vres)   # kernel maps, point lists, corner tables
-        if self._identity_fusion:
-            pass
-        elif self.two_streams:
-            main = torch.cuda.current_stream(dev)
-            if self._side is None:
-                self._side = _lib.side_stream(dev, _lib.SIDE_PAIR)
-            self._side.wait_stream(main)
-            with torch.cuda.stream(self._side):
-                gi(PointTensor(hx_i[:, :chi], r_coords), PointTensor(hx_i[:, chi:], r_coords), out=values[:, chv:])
-            gv(PointTensor(hx_v[:, :chv], r_coords), PointTensor(hx_v[:, chv:], r_coords), out=values[:, :chv])
-            main.wait_stream(self._side)
+            pts_c, r_coords = self._aligned_coords(updated, interval, origin, inputs, i)
+            self._convgru_pair(scale, hx_v, hx_i, r_coords, values)
+        self._update_map(scale, updated, values, dev)
+        return self._out_coords(i, updated, interval, pts_c), values, tsdf_target, occ_target
+
+    def _fuse_training(self, scale, i, cur_c, cur_f, dim, interval, rel_l, origin, inputs, dev):
+        """training: the map rows are state (the reference detaches the map at the start of every forward,
+        models/gru_fusion.py:260-263); the fragment's rows keep their graph through an index gather"""
+        gmap = self.global_volume[scale]
+        chv, cin = self.ch_voxel[scale], self.ch_in[scale]
+        updated, src_cur, src_glob, _ = gmap.crop_union(cur_c, cur_f, dim, interval, rel_l)
+        h_all = gmap.gather(src_glob, 0, cin, torch.empty((updated.shape[0], cin), dtype=torch.float32, device=dev))
+        pad = torch.cat([cur_f, cur_f.new_zeros((1, cin))])
+        x_all = pad[torch.where(src_cur >= 0, src_cur, torch.full_like(src_cur, cur_f.shape[0])).long()]
+        tsdf_target, occ_target = self._fuse_targets(scale, i, dim, rel_l, updated, inputs)
+        pts_c = None
+        if self._identity_fusion:      # tests: the bookkeeping alone (the fragment's rows pass through)
+            values = x_all
         else:
-            gv(PointTensor(hx_v[:, :chv], r_coords), PointTensor(hx_v[:, chv:], r_coords), out=values[:, :chv])
-            gi(PointTensor(hx_i[:, :chi], r_coords), PointTensor(hx_i[:, chi:], r_coords), out=values[:, chv:])
-        gmap.update(st.updated, values)                                          # update_map (:195-215)
-        if self._xchg is not None:
-            self._map_ready = torch.cuda.current_stream(dev).record_event()
-        tsdf_target = st.tsdf_target
-        occ_target = tsdf_target.abs() < 1 if tsdf_target is not None else None
-        return st.out_coords, values, tsdf_target, occ_target
+            pts_c, r_coords = self._aligned_coords(updated, interval, origin, inputs, i)
+            gv, gi = self.fusion_nets_voxel[scale], self.fusion_nets_img[scale]
+            vv = gv(PointTensor(h_all[:, :chv], r_coords), PointTensor(x_all[:, :chv], r_coords))
+            vi = gi(PointTensor(h_all[:, chv:], r_coords), PointTensor(x_all[:, chv:], r_coords))
+            values = torch.cat([vv, vi], dim=1)
+        self._update_map(scale, updated, values.detach().contiguous(), dev)
+        return self._out_coords(i, updated, interval, pts_c), values, tsdf_target, occ_target
 
     def forward(self, coords, values_in, inputs, scale=2, outputs=None, save_mesh=False, panoptic_infos=None):
         """coords int[N,4] (b,x,y,z) finest units, values_in f32[N,C] ->
@@ -269,113 +344,30 @@ class GRUFusion(nn.Module):
         occ_target bool[N',1] | None)   (models/gru_fusion.py:259-394)"""
         if self.direct_substitude:
             return self._scene.forward(coords, values_in, inputs, scale, outputs, save_mesh, panoptic_infos)
-        cfg = self.cfg
         batch_size = len(inputs["fragment"])
-        interval = 2 ** (cfg.N_LAYER - scale - 1)
-        dim = cfg.N_VOX[0] // interval
-        voxel_size = cfg.VOXEL_SIZE * interval
+        interval = 2 ** (self.cfg.N_LAYER - scale - 1)
+        dim = self.cfg.N_VOX[0] // interval
         dev = values_in.device
         coords = coords if coords.dtype == torch.int32 else coords.to(torch.int32)
-        chv = self.ch_voxel[scale]
-        out_c, out_v, out_t, out_o = [], [], [], []
+        out_c, out_v, out_t, out_o = outs = [], [], [], []
         if batch_size == 1:
             bounds = [0, coords.shape[0]]
         else:  # rows are grouped by ascending batch index (models/neucon_network.py:246-251): one host read
             bounds = [0] + torch.cumsum(torch.bincount(coords[:, 0].long(), minlength=batch_size), 0).tolist()
         for i in range(batch_size):
             rel = self._begin_fragment(scale, inputs, i, dev)
-            origin = inputs["vol_origin_partial"][i]
             lo, hi = bounds[i], bounds[i + 1]
             if hi == lo:
                 continue
-            cur_c, cur_f = coords[lo:hi], values_in[lo:hi]
-            gmap = self.global_volume[scale]
-            rel_l = rel.tolist()
-            if self.stage_call and dev.type == "cuda" and not torch.is_grad_enabled() and cur_f.stride(1) == 1:
-                res = self._fuse_staged(scale, i, cur_c, cur_f, dim, interval, rel_l, origin, inputs, dev)
-                for part, lst in zip(res, (out_c, out_v, out_t, out_o)):
-                    if part is not None:
-                        lst.append(part)
-                continue
-            updated, src_cur, src_glob, _ = gmap.crop_union(cur_c, cur_f, dim, interval, rel_l)
-            n_u, cin = updated.shape[0], self.ch_in[scale]
-            chi = cin - chv
-            recording = torch.is_grad_enabled() and values_in.requires_grad
-            if recording:
-                # training: the map rows are state (the reference detaches the map at the start of every forward,
-                # models/gru_fusion.py:260-263); the fragment's rows keep their graph through an index gather
-                h_all = gmap.gather(src_glob, 0, cin, torch.empty((n_u, cin), dtype=torch.float32, device=dev))
-                pad = torch.cat([cur_f, cur_f.new_zeros((1, cin))])
-                x_all = pad[torch.where(src_cur >= 0, src_cur, torch.full_like(src_cur, cur_f.shape[0])).long()]
-            else:
-                # current / global rows gathered straight into the [h | x] buffers of the two ConvGRUs (voxel
-                # channels and image channels): h = the map's row, x = the fragment's row; no concat / slice copies
-                hx_v = torch.empty((n_u, 2 * chv), dtype=torch.float32, device=dev)
-                hx_i = torch.empty((n_u, 2 * chi), dtype=torch.float32, device=dev)
-                gmap.gather(src_glob, 0, chv, hx_v[:, :chv])
-                gmap.gather(src_glob, chv, chi, hx_i[:, :chi])
-                gather_rows(cur_f[:, :chv], src_cur, chv, out=hx_v[:, chv:])
-                gather_rows(cur_f[:, chv:], src_cur, chi, out=hx_i[:, chi:])
-
-            tsdf_target = occ_target = None
-            if "occ_list" in inputs:
-                lvl = cfg.N_LAYER - scale - 1
-                tsdf_target = self.target_tsdf_volume[scale].target_fuse(
-                    inputs["tsdf_list"][lvl][i], inputs["occ_list"][lvl][i], dim, rel_l, updated)
-                occ_target = tsdf_target.abs() < 1
-
-            values = None if recording else torch.empty((n_u, cin), dtype=torch.float32, device=dev)
-            pts_c = None
-            if recording and self._identity_fusion:
-                values = x_all
-            elif recording:
-                pts_c = torch.cat([torch.zeros_like(updated[:, :1]), updated * interval], dim=1)
-                r_coords = aligned_camera_coords(pts_c, origin.reshape(1, 3), cfg.VOXEL_SIZE,
-                                                 inputs["world_to_aligned_camera"][i].reshape(1, 4, 4))
-                gv, gi = self.fusion_nets_voxel[scale], self.fusion_nets_img[scale]
-                vv = gv(PointTensor(h_all[:, :chv], r_coords), PointTensor(x_all[:, :chv], r_coords))
-                vi = gi(PointTensor(h_all[:, chv:], r_coords), PointTensor(x_all[:, chv:], r_coords))
-                values = torch.cat([vv, vi], dim=1)
-            elif not self._identity_fusion:
-                pts_c = torch.cat([torch.zeros_like(updated[:, :1]), updated * interval], dim=1)
-                r_coords = aligned_camera_coords(pts_c, origin.reshape(1, 3), cfg.VOXEL_SIZE,
-                                                 inputs["world_to_aligned_camera"][i].reshape(1, 4, 4))
-                # both cells see the same points: their six SConv3d share two voxelisations (torchsparse_utils)
-                gv, gi = self.fusion_nets_voxel[scale], self.fusion_nets_img[scale]
-                if self.two_streams and dev.type == "cuda" and not torch.is_grad_enabled():
-                    # the shared voxelisations are built first; the two cells (independent channel groups) then run
-                    # on two HIP streams: each is a chain of small kernels that leaves most CUs idle on its own
-                    prepare_convgru_voxelizations(r_coords, gv.convz.pres, gv.convz.vres)
-                    main = torch.cuda.current_stream(dev)
-                    if self._side is None:
-                        self._side = _lib.side_stream(dev, _lib.SIDE_PAIR)
-                    self._side.wait_stream(main)
-                    with torch.cuda.stream(self._side):
-                        gi(PointTensor(hx_i[:, :chi], r_coords), PointTensor(hx_i[:, chi:], r_coords), out=values[:, chv:])
-                    gv(PointTensor(hx_v[:, :chv], r_coords), PointTensor(hx_v[:, chv:], r_coords), out=values[:, :chv])
-                    main.wait_stream(self._side)
-                else:
-                    gv(PointTensor(hx_v[:, :chv], r_coords), PointTensor(hx_v[:, chv:], r_coords), out=values[:, :chv])
-                    gi(PointTensor(hx_i[:, :chi], r_coords), PointTensor(hx_i[:, chi:], r_coords), out=values[:, chv:])
-            else:
-                values[:, :chv], values[:, chv:] = hx_v[:, chv:], hx_i[:, chi:]
-
-            gmap.update(updated, values.detach().contiguous() if recording else values)    # update_map (:195-215)
-            if self._xchg is not None and dev.type == "cuda":
-                self._map_ready = torch.cuda.current_stream(dev).record_event()
-            if self._xchg is not None and dev.type != "cuda":   # (reference path; on the GPU update() stamps the rows itself)
-                rel_t = torch.tensor(rel_l, dtype=torch.int32, device=dev)
-                self._xchg.mark_fused(scale, updated + rel_t, self._cur_fragment)
-
-            # (batch element 0: the rows the aligned-camera transform was given are these coordinates already)
-            out_c.append(pts_c if (i == 0 and pts_c is not None) else
-                         torch.cat([torch.full_like(updated[:, :1], i), updated * interval], dim=1))
-            out_v.append(values)
-            if tsdf_target is not None:
-                out_t.append(tsdf_target)
-                out_o.append(occ_target)
+            cur_f = values_in[lo:hi]
+            fuse = (self._fuse_training if torch.is_grad_enabled() and values_in.requires_grad else
+                    self._fuse_staged if self.stage_call and not torch.is_grad_enabled() and cur_f.stride(1) == 1 else
+                    self._fuse_separate)
+            parts = fuse(scale, i, coords[lo:hi], cur_f, dim, interval, rel.tolist(), inputs["vol_origin_partial"][i], inputs, dev)
+            for part, lst in zip(parts, outs):
+                if part is not None:
+                    lst.append(part)
         if not out_c:
             return None, None, None, None
         cat1 = lambda parts: parts[0] if len(parts) == 1 else torch.cat(parts)     # (one batch element: no copy)
-        coords_all = cat1(out_c).to(self.coords_dtype)
-        return (coords_all, cat1(out_v), cat1(out_t) if out_t else None, cat1(out_o) if out_o else None)
+        return (cat1(out_c).to(self.coords_dtype), cat1(out_v), cat1(out_t) if out_t else None, cat1(out_o) if out_o else None)

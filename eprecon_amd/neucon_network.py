@@ -14,13 +14,16 @@ signature and early-return conventions:
      post-processing                                                              (:516-587)
 Every sparse / gather / scatter step runs in libeprecon_hip.so; the dense heads are PyTorch-ROCm.
 """
+import os
 import sys
+from collections import namedtuple
 
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import _lib
+from . import back_project as BP
 from . import grid_ops as GO
 from . import sparse as SP
 from .back_project import Back_Project
@@ -38,12 +41,12 @@ from .torchsparse_utils import SpvcnnPrefetch, aligned_camera_coords
 
 # the reference's sequence of torch calls (threshold, index_add counts, nonzero, index_select x 4, cat: ~15 launches and two
 # host reads per level) stays for training and the seeded random drop; inference takes eprecon_sparsify_async (3 launches, one
-# host read).  Tests flip this module attribute to compare the two.
+# host read).  tests/test_switches_gpu.py runs whole scenes with this attribute off; tests/test_sparsify_gpu.py compares the calls.
 _FUSED_SPARSIFY = True
 # EPRECON_PREFETCH=0: every SPVCNN pass reads the sizes of its voxel sets itself and the panoptic pruning reads its own counts
 # (round 4: 14 blocking reads per fragment) instead of queueing that work on the DEVICE count of the rows a compaction has just
 # written and letting its counts ride on the compaction's read (torchsparse_utils.SpvcnnPrefetch: 10 reads).  Same results.
-_PREFETCH = __import__("os").environ.get("EPRECON_PREFETCH", "1") == "1"
+_PREFETCH = os.environ.get("EPRECON_PREFETCH", "1") == "1"
 
 
 WARN_TAG = ""    # prefix of the guard warnings below; fragment_step.calibrate_occupancy_heads sets "[calibration] " around its forwards
@@ -51,6 +54,35 @@ WARN_TAG = ""    # prefix of the guard warnings below; fragment_step.calibrate_o
 
 def _warn(msg):
     print(f"[eprecon_amd] {WARN_TAG}warning: {msg}", file=sys.stderr)
+
+
+def sparsify_guards(scale, occupied, on_target, has_target, training, cap, sampled=False, exceed_num=EXCEED_NUM,
+                    min_occ=STAGE_MIN_OCC):
+    """The guards in front of a level's compaction (models/neucon_network.py:463-497) on host integers: occupied[b] / on_target[b]
+    = voxels of batch element b over the occupancy threshold / those whose target is occupied too -> (subsample, warning).
+    `warning`: the text of the guard that ends the forward (None: go on).  `subsample`: in the reference's order up to that guard,
+    the batch elements to cut down to `cap` rows first; the rows on target then change, so the target guard is left open: the
+    caller drops the rows, counts again and asks with sampled=True for that guard alone.  (`training` is True on the reference's
+    test path, main.py:357: the caps are live there.)"""
+    subsample = []
+    if not sampled:
+        for b, num_batch in enumerate(occupied):
+            if num_batch < min_occ:
+                return subsample, f"no valid points: scale {scale}"
+            if training and num_batch > cap * exceed_num:
+                return subsample, f"exceed too many points: scale {scale} num_batch {num_batch}"
+            if training and num_batch > cap:
+                subsample.append(b)
+        if subsample:
+            return subsample, None
+    if has_target and any(n == 0 for n in on_target):
+        return subsample, f"occ_target is 0: scale {scale}"
+    return subsample, None
+
+
+# what a level hands on: its kept rows (coordinates, TSDF, [features | tsdf | occ], [features | image features]), the mask / target
+# the panoptic loss reads, what its compaction queued ahead ((up_coords, r_coords) of the next level; the pruning behind the last)
+_Level = namedtuple("_Level", "pre_coords pre_tsdf pre_feat kept_all occupancy occ_target ahead", defaults=(None,) * 7)
 
 
 class NeuConNet(nn.Module):
@@ -155,9 +187,7 @@ class NeuConNet(nn.Module):
         occ_init, coord_init, _ = init_output
         # (the same host read checks that every voxel of the initialisation set was on the dense grid its convolutions ran on)
         selected, _ = GO.init_select(occ_init, coord_init, bs, dim=shape_init[0] // 2 ** INIT_STAGE,
-                                     cell=2 ** self.n_scales, threshold=INIT_OCC_THRESHOLD,
-                                     must_be_zero=getattr(self.initialization, "dense_checks", ()),
-                                     dense=getattr(self.initialization, "dense_map", None))
+                                     cell=2 ** self.n_scales, threshold=INIT_OCC_THRESHOLD, dense=self.initialization.dense_map)
         return init_output, selected, shape_init
 
     def _spvcnn_behind(self, level, inputs, children):
@@ -179,9 +209,7 @@ class NeuConNet(nn.Module):
         """the ancestor pruning of levels 1 and 0 (prune_to_ancestors) queued on the device count of the finest level's kept
         rows; finish -> (keep1, keep0, n1, n0)"""
         def behind(fine, n_dev, extra_out):
-            dev = fine.device
-            keep1 = SP.HashGrid(fine.shape[0], dev).build(fine, quantum=2, n_dev=n_dev).query(coords1.contiguous()) >= 0
-            keep0 = SP.HashGrid(fine.shape[0], dev).build(fine, quantum=4, n_dev=n_dev).query(coords0.contiguous()) >= 0
+            keep1, keep0 = NeuConNet.prune_to_ancestors([coords0, coords1, fine], n_dev)
             extra_out.copy_(torch.stack([keep1.sum(), keep0.sum()]))
             return lambda m, host: (keep1, keep0, int(host[0]), int(host[1]))
         behind.n_extra = 2       # the two kept-row counts
@@ -203,16 +231,15 @@ class NeuConNet(nn.Module):
                 self.gru_fusion.exchange_boundaries(inputs, b)
 
         # ---- A. occupancy initialisation ("depth prior") -------------------------------------
-        scale = self.n_scales - INIT_STAGE
-        init_output, coord_init_selected, shape_init = self._init_stage(features, inputs, bs, dev, select=not only_train_init)
+        init_output, coord_init_selected, _ = self._init_stage(features, inputs, bs, dev, select=not only_train_init)
         if init_output is None:
             loss_dict["occupancy_initialization_loss"] = zero
             _warn("no valid points in initialization")
             outputs["init_overlap_count"] = init_overlap_count
             return outputs, loss_dict
-        occ_init, coord_init, count_init = init_output
+        occ_init, coord_init, _ = init_output
         if only_train_init:    # :267-292
-            tsdf_init_target, occ_init_target = self.get_target_init(coord_init, inputs, scale)
+            tsdf_init_target, occ_init_target = self.get_target_init(coord_init, inputs, self.n_scales - INIT_STAGE)
             hit = occ_init.detach().sigmoid().reshape(-1) > INIT_OCC_THRESHOLD
             losses = []
             for b in range(bs):
@@ -226,221 +253,204 @@ class NeuConNet(nn.Module):
         self._record(stage="init", occ_init=occ_init, coord_init=coord_init, selected=coord_init_selected)
 
         # ---- B. coarse-to-fine surface reconstruction ----------------------------------------
-        pre_feat = pre_coords = None
-        panoptic_voxel_feats, panoptic_coords = [], []
-        occ_target = occupancy = None
         # inference on the GPU: the coordinate side of every SPVCNN pass (and the panoptic pruning) is queued on the device
         # count of the rows the previous compaction wrote, and its sizes ride on that compaction's host read
         prefetch = _PREFETCH and dev.type == "cuda" and not recording and _FUSED_SPARSIFY
-        ahead = pruned = None        # (up_coords, r_coords) of the level about to run; (keep1, keep0, n1, n0)
+        levels = []
+        level = _Level(pre_coords=coord_init_selected)
         for i in range(cfg.N_LAYER):
-            interval = 2 ** (self.n_scales - i)
-            scale = self.n_scales - i
-            ready, ahead = ahead, None
-            if i == 0:
-                up_coords = coord_init_selected.contiguous()
-                min_view_number = 2
-                up_feat = None
-            else:
-                if ready is not None and ready[0] is not None and ready[0].shape[0] == 8 * pre_coords.shape[0]:
-                    up_feat, up_coords = GO.upsample(pre_feat, pre_coords, interval, up_coords=ready[0])
-                else:
-                    ready = None
-                    up_feat, up_coords = self.upsample(pre_feat, pre_coords, interval)
-                min_view_number = 0
-            feats = stack_views([f[scale] for f in features_backbone2d_occ_pano])   # no copy for batched backbones
-            KRcam = inputs["proj_matrices"][:, :, scale].permute(1, 0, 2, 3).contiguous()
-            if i == 0 and prefetch and up_coords.dtype == torch.int32:
-                from . import back_project as BP
-                project_output, ready = BP.forward_behind(self.back_projection[0], up_coords, inputs["vol_origin_partial"],
-                                                          cfg.VOXEL_SIZE, feats, KRcam, min_view_number,
-                                                          self._spvcnn_behind(0, inputs, children=False))
-            else:
-                project_output = self.back_projection[i](up_coords, inputs["vol_origin_partial"], cfg.VOXEL_SIZE,
-                                                         feats, KRcam, min_view_number)
-            if project_output is None:
+            up_feat, up_coords, ready = self._level_input(i, level)
+            passed = self._level_features(i, up_feat, up_coords, ready, features_backbone2d_occ_pano, inputs, prefetch)
+            if passed is None:
                 loss_dict[f"tsdf_occ_loss_{i}"] = zero
                 _warn(f"no valid points in back_projection: scale {i}")
                 return outputs, loss_dict
-            volume, up_coords, _, _, count = project_output
-            if i != 0:
-                if min_view_number <= 0:       # (the view count is never negative: every voxel is kept, no host read)
-                    feat = torch.cat([volume, up_feat], dim=1)
-                else:
-                    keep = count >= min_view_number
-                    feat = torch.cat([volume, up_feat if bool(keep.all()) else up_feat[keep]], dim=1)
+            heads = self._fuse_and_heads(i, *passed, inputs, loss_dict, zero, recording)
+            if _FUSED_SPARSIFY and dev.type == "cuda" and not recording and heads[2].stride(1) == 1:
+                level = self._sparsify_fused(i, *heads, bs, levels, inputs, prefetch)
             else:
-                feat = volume
-
-            if ready is not None and ready[1].shape[0] == up_coords.shape[0]:
-                r_coords = ready[1]        # (queued ahead with the voxelisation the SPVCNN pass below finds in the cache)
-            else:
-                r_coords = aligned_camera_coords(up_coords, inputs["vol_origin_partial"], cfg.VOXEL_SIZE,
-                                                 inputs["world_to_aligned_camera"])
-            sp_in = feat
-            feat = self.sp_convs[i](PointTensor(feat.contiguous(), r_coords))
-            feat_all = torch.cat([feat, volume], dim=-1)
-            self._record(stage=f"spvcnn{i}", coords=up_coords, feat_in=sp_in, r_coords=r_coords, feat_out=feat,
-                         volume=volume)
-
-            tsdf_target = None
-            if not cfg.FUSION.FUSION_ON and "occ_list" in inputs:
-                tsdf_target, occ_target = self.get_target(up_coords, inputs, scale)
-            if cfg.FUSION.FUSION_ON:
-                voxel_dim = feat.shape[-1]
-                fuse_in = (up_coords, feat_all)
-                up_coords, feat_all, tsdf_target, occ_target = self.gru_fusion(up_coords, feat_all, inputs, i)
-                feat = feat_all[:, :voxel_dim]
-                self._record(stage=f"gru{i}", coords_in=fuse_in[0], feat_in=fuse_in[1], coords=up_coords,
-                             feat_all=feat_all, tsdf_target=tsdf_target)
-            tsdf, occ = linear4x_pair(self.tsdf_preds[i], self.occ_preds[i], feat)
-            if recording and tsdf_target is not None:   # :441-449 (grid_mask is all ones with FUSION.FULL)
-                loss_dict[f"tsdf_occ_loss_{i}"] = compute_loss(tsdf, occ, tsdf_target, occ_target, pos_weight=cfg.POS_WEIGHT)
-            else:
-                loss_dict[f"tsdf_occ_loss_{i}"] = zero
-
-            # ---- sparsify for the next stage (:454-507) ----
-            # (the reference's grid_mask is all ones on this path, `occupancy[grid_mask == False] = False` is a no-op)
-            # Inference on the GPU: threshold, the guards' counts and the compaction of the kept rows in ONE call and one host
-            # read (csrc/grid_ops.hip, eprecon_sparsify_async); the random sub-sampling branch and training keep the
-            # reference's sequence of torch calls below.
-            fused = None
-            if _FUSED_SPARSIFY and dev.type == "cuda" and not recording and feat_all.stride(1) == 1:
-                behind = None
-                if prefetch and i + 1 < cfg.N_LAYER:
-                    behind = self._spvcnn_behind(i + 1, inputs, children=True)
-                elif prefetch and i + 1 == cfg.N_LAYER and len(panoptic_coords) == 2 and bs == 1 \
-                        and all(c.dtype == torch.int32 for c in panoptic_coords):
-                    behind = self._prune_behind(panoptic_coords[1], panoptic_coords[0])
-                fused = GO.sparsify(occ, cfg.THRESHOLDS[i], occ_target,
-                                    up_coords if up_coords.dtype == torch.int32 else up_coords.to(torch.int32), tsdf, feat_all,
-                                    feat.shape[1], bs, behind=behind)
-                if self.training and any(cfg.TRAIN_NUM_SAMPLE[i] < nb <= cfg.TRAIN_NUM_SAMPLE[i] * EXCEED_NUM
-                                         for nb in fused[0][1:1 + bs]):
-                    fused = None          # a batch element is over its cap: np.random.choice drops rows first (below)
-                elif behind is not None:
-                    if i + 1 < cfg.N_LAYER:
-                        ahead = fused[6]
-                    else:
-                        pruned = fused[6]
-            if fused is not None:
-                stats = [fused[0][1:1 + bs], fused[0][1 + bs:1 + 2 * bs]]
-                if self.trace is not None:
-                    self._record(stage=f"heads{i}", feat=feat, tsdf=tsdf, occ=occ, occupancy=occ.squeeze(1) > cfg.THRESHOLDS[i])
-                for b in range(bs):
-                    if stats[0][b] < STAGE_MIN_OCC:
-                        _warn(f"no valid points: scale {i}")
-                        return outputs, loss_dict
-                    if self.training and stats[0][b] > cfg.TRAIN_NUM_SAMPLE[i] * EXCEED_NUM:
-                        _warn(f"exceed too many points: scale {i} num_batch {stats[0][b]}")
-                        return outputs, loss_dict
-                if occ_target is not None:
-                    for b in range(bs):
-                        if stats[1][b] == 0:
-                            _warn(f"occ_target is 0: scale {i}")
-                            return outputs, loss_dict
-                _, pre_coords, pre_tsdf, pre_occ, kept_all, pre_feat = fused[:6]
-                if pre_coords.dtype != up_coords.dtype:
-                    pre_coords = pre_coords.to(up_coords.dtype)
-                panoptic_voxel_feats.append(kept_all)
-                panoptic_coords.append(pre_coords)
-                if i == cfg.N_LAYER - 1:
-                    outputs["coords"] = pre_coords
-                    outputs["tsdf"] = pre_tsdf
-                continue
-            occupancy = occ.squeeze(1) > cfg.THRESHOLDS[i]
-            # recorded before the guards so that an early return still leaves the logits visible;
-            # `occupancy` is the same tensor object the sub-sampling below edits in place
-            self._record(stage=f"heads{i}", feat=feat, tsdf=tsdf, occ=occ, occupancy=occupancy)
-            # per batch element: occupied voxels, and occupied voxels whose target is occupied — ONE host read
-            # for all the guards below (the reference synchronises once per guard and batch element)
-            bcol = up_coords[:, 0].long()
-            tgt = occ_target.reshape(-1) if occ_target is not None else torch.ones_like(occupancy)   # [N] (get_target) or [N,1] (fusion)
-            count_by_batch = lambda: torch.zeros((2, bs), dtype=torch.int64, device=dev).index_add_(
-                1, bcol, torch.stack([occupancy, occupancy & tgt]).long()).tolist()
-            stats = count_by_batch()
-            dropped = False
-            for b in range(bs):
-                num_batch = stats[0][b]
-                if num_batch < STAGE_MIN_OCC:
-                    _warn(f"no valid points: scale {i}")
-                    return outputs, loss_dict
-                cap = cfg.TRAIN_NUM_SAMPLE[i]
-                # self.training is True on the reference's test path (main.py:357): the caps are live
-                if self.training and num_batch > cap * EXCEED_NUM:
-                    _warn(f"exceed too many points: scale {i} num_batch {num_batch}")
-                    return outputs, loss_dict
-                elif self.training and num_batch > cap:
-                    _warn(f"choice too many points: scale {i} num_batch {num_batch}")
-                    batch_ind = torch.nonzero(up_coords[:, 0] == b).squeeze(1)
-                    choice = np.random.choice(num_batch, num_batch - cap, replace=False)
-                    ind = torch.nonzero(occupancy[batch_ind]).squeeze(1)
-                    drop = batch_ind[ind[torch.from_numpy(choice).to(ind.device)]]
-                    occupancy[drop] = False
-                    dropped = True
-            if occ_target is not None:
-                if dropped:
-                    stats = count_by_batch()
-                for b in range(bs):
-                    if stats[1][b] == 0:
-                        _warn(f"occ_target is 0: scale {i}")
-                        return outputs, loss_dict
-            keep_rows = torch.nonzero(occupancy).squeeze(1)
-            pre_coords = up_coords.index_select(0, keep_rows)
-            pre_tsdf, pre_occ = tsdf.index_select(0, keep_rows), occ.index_select(0, keep_rows)
-            kept_all = feat_all.index_select(0, keep_rows)
-            panoptic_voxel_feats.append(kept_all)
-            panoptic_coords.append(pre_coords)
-            pre_feat = torch.cat([kept_all[:, :feat.shape[1]], pre_tsdf, pre_occ], dim=1)
-            if i == cfg.N_LAYER - 1:
-                outputs["coords"] = pre_coords
-                outputs["tsdf"] = pre_tsdf
+                level = self._sparsify_torch(i, *heads, bs)
+            if level is None:          # a guard fired (and warned)
+                return outputs, loss_dict
+            levels.append(level)
+        outputs["coords"], outputs["tsdf"] = level.pre_coords, level.pre_tsdf
 
         # ---- C. panoptic segmentation (:516-587) ---------------------------------------------------
+        panoptic_coords, panoptic_voxel_feats = [l.pre_coords for l in levels], [l.kept_all for l in levels]
         side = self.panoptic_stream if (not recording and dev.type == "cuda" and self.panoptic is not None) else None
-        if side is None:
-            self._panoptic_branch(panoptic_coords, panoptic_voxel_feats, bs, outputs, pruned)
+        if side is not None:
+            self._panoptic_pipelined(side, panoptic_coords, panoptic_voxel_feats, bs, outputs, level.ahead, dev)
+        else:
+            self._panoptic_branch(panoptic_coords, panoptic_voxel_feats, bs, outputs, level.ahead)
             if self.panoptic is not None:
                 outputs["panoptic_info"] = [panoptic_post(o) for o in outputs["panoptic_out"]]  # :583-587
-                if recording and "rgb_list" in inputs and occ_target is not None:
-                    loss_dict["panoptic_loss"] = self._panoptic_loss(outputs["panoptic_out"], panoptic_coords[2], occ_target,
-                                                                     occupancy, inputs, bs)
-        else:
-            # Pipelined serving (opt-in, NeuConNet.panoptic_stream): the panoptic branch of THIS fragment is queued on its
-            # own stream and the call returns; its ~400 small launches then overlap with the front of the NEXT fragment
-            # (it reads only this fragment's tensors, never the scene map).  The host-synchronising post-processing is
-            # deferred: outputs["panoptic_finish"]() waits for the branch, fills outputs["panoptic_info"] and returns outputs.
-            main = torch.cuda.current_stream(dev)
-            side.wait_stream(main)
-            for t in list(panoptic_voxel_feats) + list(panoptic_coords) + (list(pruned[:2]) if pruned is not None else []):
-                t.record_stream(side)       # allocated on the main stream, read on the side stream after this call returns
-            def branch(outputs=outputs, coords=panoptic_coords, feats=panoptic_voxel_feats, side=side, pruned=pruned):
-                # (grad mode and the current stream are thread-local: both are set here)
-                with torch.no_grad(), torch.cuda.stream(side):
-                    self._panoptic_branch(coords, feats, bs, outputs, pruned)
-                    if self.panoptic_worker is not None:
-                        # the host-synchronising post-processing too: it is the worker that waits for the decoder
-                        outputs["panoptic_info"] = [panoptic_post(o) for o in outputs["panoptic_out"]]
-                    return side.record_event()
-
-            # With a worker thread the ~400 launches of the branch are issued while the main thread sits in the blocking
-            # count reads of the NEXT fragment (the GIL is released there); without one they are issued inline.
-            job = self.panoptic_worker.submit(branch) if self.panoptic_worker is not None else None
-            done = None if job is not None else branch()
-
-            def finish(outputs=outputs, job=job, done=done, side=side):
-                (job.result() if job is not None else done).synchronize()
-                if "panoptic_info" not in outputs:      # inline mode: deferred to here so that forward() did not block
-                    with torch.cuda.stream(side):
-                        outputs["panoptic_info"] = [panoptic_post(o) for o in outputs["panoptic_out"]]
-                    side.synchronize()
-                outputs.pop("panoptic_finish", None)
-                return outputs
-            outputs["panoptic_finish"] = finish
+                if recording and "rgb_list" in inputs and level.occ_target is not None:
+                    loss_dict["panoptic_loss"] = self._panoptic_loss(outputs["panoptic_out"], panoptic_coords[2],
+                                                                     level.occ_target, level.occupancy, inputs, bs)
         self._record(stage="panoptic", coords=panoptic_coords, feats=panoptic_voxel_feats)
         if recording:
             _lib.drain_deferred()   # training has no fused sparsify read: the back-projections' deferred row-count checks are verified here
         return outputs, loss_dict
+
+    def _level_input(self, i, prev):
+        """the voxels level i starts from -> (up_feat | None, up_coords, ready): the stage-0 selection, or the eight children of
+        every row level i - 1 kept (`ready`: their coordinates and aligned coordinates, when that level queued them ahead)"""
+        if i == 0:
+            return None, prev.pre_coords.contiguous(), None
+        interval = 2 ** (self.n_scales - i)
+        ready = prev.ahead
+        if ready is not None and ready[0] is not None and ready[0].shape[0] == 8 * prev.pre_coords.shape[0]:
+            return GO.upsample(prev.pre_feat, prev.pre_coords, interval, up_coords=ready[0]) + (ready,)
+        return self.upsample(prev.pre_feat, prev.pre_coords, interval) + (None,)
+
+    def _level_features(self, i, up_feat, up_coords, ready, features_2d, inputs, prefetch):
+        """Back_Project, concat, aligned-camera coordinates, SPVCNN -> (up_coords, feat, feat_all) | None (no voxel was kept)"""
+        cfg = self.cfg
+        scale = self.n_scales - i
+        min_view_number = 2 if i == 0 else 0
+        feats = stack_views([f[scale] for f in features_2d])   # no copy for batched backbones
+        KRcam = inputs["proj_matrices"][:, :, scale].permute(1, 0, 2, 3).contiguous()
+        if i == 0 and prefetch and up_coords.dtype == torch.int32:
+            project_output, ready = BP.forward_behind(self.back_projection[0], up_coords, inputs["vol_origin_partial"],
+                                                      cfg.VOXEL_SIZE, feats, KRcam, min_view_number,
+                                                      self._spvcnn_behind(0, inputs, children=False))
+        else:
+            project_output = self.back_projection[i](up_coords, inputs["vol_origin_partial"], cfg.VOXEL_SIZE,
+                                                     feats, KRcam, min_view_number)
+        if project_output is None:
+            return None
+        volume, up_coords = project_output[:2]
+        # (above level 0 min_view_number is 0 and the view count is never negative: every voxel is kept, no host read)
+        feat = volume if i == 0 else torch.cat([volume, up_feat], dim=1)
+        if ready is not None and ready[1].shape[0] == up_coords.shape[0]:
+            r_coords = ready[1]        # (queued ahead with the voxelisation the SPVCNN pass below finds in the cache)
+        else:
+            r_coords = aligned_camera_coords(up_coords, inputs["vol_origin_partial"], cfg.VOXEL_SIZE,
+                                             inputs["world_to_aligned_camera"])
+        sp_in = feat
+        feat = self.sp_convs[i](PointTensor(feat.contiguous(), r_coords))
+        self._record(stage=f"spvcnn{i}", coords=up_coords, feat_in=sp_in, r_coords=r_coords, feat_out=feat, volume=volume)
+        return up_coords, feat, torch.cat([feat, volume], dim=-1)
+
+    def _fuse_and_heads(self, i, up_coords, feat, feat_all, inputs, loss_dict, zero, recording):
+        """GRU fusion into the scene map, the two heads, the level's loss -> (up_coords, feat, feat_all, tsdf, occ, occ_target)"""
+        cfg = self.cfg
+        tsdf_target = occ_target = None
+        if cfg.FUSION.FUSION_ON:
+            voxel_dim = feat.shape[-1]
+            fuse_in = (up_coords, feat_all)
+            up_coords, feat_all, tsdf_target, occ_target = self.gru_fusion(up_coords, feat_all, inputs, i)
+            feat = feat_all[:, :voxel_dim]
+            self._record(stage=f"gru{i}", coords_in=fuse_in[0], feat_in=fuse_in[1], coords=up_coords,
+                         feat_all=feat_all, tsdf_target=tsdf_target)
+        elif "occ_list" in inputs:
+            tsdf_target, occ_target = self.get_target(up_coords, inputs, self.n_scales - i)
+        tsdf, occ = linear4x_pair(self.tsdf_preds[i], self.occ_preds[i], feat)
+        if recording and tsdf_target is not None:   # :441-449 (grid_mask is all ones with FUSION.FULL)
+            loss_dict[f"tsdf_occ_loss_{i}"] = compute_loss(tsdf, occ, tsdf_target, occ_target, pos_weight=cfg.POS_WEIGHT)
+        else:
+            loss_dict[f"tsdf_occ_loss_{i}"] = zero
+        return up_coords, feat, feat_all, tsdf, occ, occ_target
+
+    def _sparsify_fused(self, i, up_coords, feat, feat_all, tsdf, occ, occ_target, bs, levels, inputs, prefetch):
+        """sparsify for the next stage (:454-507) -> _Level | None (a guard fired and warned).  Inference on the GPU: threshold,
+        the guards' counts and the compaction of the kept rows in ONE call and one host read (csrc/grid_ops.hip,
+        eprecon_sparsify_async), with the next level's coordinate side (or, behind the finest level, the panoptic pruning)
+        queued in front of that read.  The random sub-sampling goes to _sparsify_torch."""
+        cfg = self.cfg
+        cap = cfg.TRAIN_NUM_SAMPLE[i]
+        behind = None
+        if prefetch and i + 1 < cfg.N_LAYER:
+            behind = self._spvcnn_behind(i + 1, inputs, children=True)
+        elif prefetch and len(levels) == 2 and bs == 1 and all(l.pre_coords.dtype == torch.int32 for l in levels):
+            behind = self._prune_behind(levels[1].pre_coords, levels[0].pre_coords)
+        fused = GO.sparsify(occ, cfg.THRESHOLDS[i], occ_target,
+                            up_coords if up_coords.dtype == torch.int32 else up_coords.to(torch.int32), tsdf, feat_all,
+                            feat.shape[1], bs, behind=behind)
+        occupied, on_target = fused[0][1:1 + bs], fused[0][1 + bs:1 + 2 * bs]
+        if self.training and any(cap < nb <= cap * EXCEED_NUM for nb in occupied):   # np.random.choice drops rows first
+            return self._sparsify_torch(i, up_coords, feat, feat_all, tsdf, occ, occ_target, bs)
+        if self.trace is not None:
+            self._record(stage=f"heads{i}", feat=feat, tsdf=tsdf, occ=occ, occupancy=occ.squeeze(1) > cfg.THRESHOLDS[i])
+        _, warning = sparsify_guards(i, occupied, on_target, occ_target is not None, self.training, cap)
+        if warning is not None:
+            _warn(warning)
+            return None
+        _, pre_coords, pre_tsdf, _, kept_all, pre_feat = fused[:6]
+        if pre_coords.dtype != up_coords.dtype:
+            pre_coords = pre_coords.to(up_coords.dtype)
+        return _Level(pre_coords, pre_tsdf, pre_feat, kept_all, None, occ_target, fused[6] if behind is not None else None)
+
+    def _sparsify_torch(self, i, up_coords, feat, feat_all, tsdf, occ, occ_target, bs):
+        """the same on the reference's sequence of torch calls: training, the seeded random drop, _FUSED_SPARSIFY off.
+        (the reference's grid_mask is all ones on this path, `occupancy[grid_mask == False] = False` is a no-op)"""
+        cfg = self.cfg
+        cap = cfg.TRAIN_NUM_SAMPLE[i]
+        occupancy = occ.squeeze(1) > cfg.THRESHOLDS[i]
+        # recorded before the guards so that an early return still leaves the logits visible;
+        # `occupancy` is the same tensor object the sub-sampling below edits in place
+        self._record(stage=f"heads{i}", feat=feat, tsdf=tsdf, occ=occ, occupancy=occupancy)
+        # per batch element: occupied voxels, and occupied voxels whose target is occupied — ONE host read
+        # for all the guards (the reference synchronises once per guard and batch element)
+        bcol = up_coords[:, 0].long()
+        has_target = occ_target is not None
+        tgt = occ_target.reshape(-1) if has_target else torch.ones_like(occupancy)   # [N] (get_target) or [N,1] (fusion)
+        count_by_batch = lambda: torch.zeros((2, bs), dtype=torch.int64, device=occ.device).index_add_(
+            1, bcol, torch.stack([occupancy, occupancy & tgt]).long()).tolist()
+        stats = count_by_batch()
+        subsample, warning = sparsify_guards(i, stats[0], stats[1], has_target, self.training, cap)
+        for b in subsample:
+            num_batch = stats[0][b]
+            _warn(f"choice too many points: scale {i} num_batch {num_batch}")
+            batch_ind = torch.nonzero(up_coords[:, 0] == b).squeeze(1)
+            choice = np.random.choice(num_batch, num_batch - cap, replace=False)
+            ind = torch.nonzero(occupancy[batch_ind]).squeeze(1)
+            drop = batch_ind[ind[torch.from_numpy(choice).to(ind.device)]]
+            occupancy[drop] = False
+        if subsample and warning is None and has_target:      # the target guard, on the counts of the rows that are left
+            _, warning = sparsify_guards(i, stats[0], count_by_batch()[1], has_target, self.training, cap, sampled=True)
+        if warning is not None:
+            _warn(warning)
+            return None
+        keep_rows = torch.nonzero(occupancy).squeeze(1)
+        pre_coords = up_coords.index_select(0, keep_rows)
+        pre_tsdf, pre_occ = tsdf.index_select(0, keep_rows), occ.index_select(0, keep_rows)
+        kept_all = feat_all.index_select(0, keep_rows)
+        pre_feat = torch.cat([kept_all[:, :feat.shape[1]], pre_tsdf, pre_occ], dim=1)
+        return _Level(pre_coords, pre_tsdf, pre_feat, kept_all, occupancy, occ_target)
+
+    def _panoptic_pipelined(self, side, panoptic_coords, panoptic_voxel_feats, bs, outputs, pruned, dev):
+        """Pipelined serving (opt-in, NeuConNet.panoptic_stream): the panoptic branch of THIS fragment is queued on its own stream,
+        the call returns; its ~400 small launches then overlap with the front of the NEXT fragment (it reads only this fragment's
+        tensors, never the scene map).  outputs["panoptic_finish"]() waits for it, fills outputs["panoptic_info"], returns them."""
+        main = torch.cuda.current_stream(dev)
+        side.wait_stream(main)
+        for t in list(panoptic_voxel_feats) + list(panoptic_coords) + (list(pruned[:2]) if pruned is not None else []):
+            t.record_stream(side)       # allocated on the main stream, read on the side stream after this call returns
+
+        def branch():
+            # (grad mode and the current stream are thread-local: both are set here)
+            with torch.no_grad(), torch.cuda.stream(side):
+                self._panoptic_branch(panoptic_coords, panoptic_voxel_feats, bs, outputs, pruned)
+                if self.panoptic_worker is not None:
+                    # the host-synchronising post-processing too: it is the worker that waits for the decoder
+                    outputs["panoptic_info"] = [panoptic_post(o) for o in outputs["panoptic_out"]]
+                return side.record_event()
+
+        # With a worker thread the ~400 launches of the branch are issued while the main thread sits in the blocking
+        # count reads of the NEXT fragment (the GIL is released there); without one they are issued inline.
+        job = self.panoptic_worker.submit(branch) if self.panoptic_worker is not None else None
+        done = None if job is not None else branch()
+
+        def finish():
+            (job.result() if job is not None else done).synchronize()
+            if "panoptic_info" not in outputs:      # inline mode: deferred to here so that forward() did not block
+                with torch.cuda.stream(side):
+                    outputs["panoptic_info"] = [panoptic_post(o) for o in outputs["panoptic_out"]]
+                side.synchronize()
+            outputs.pop("panoptic_finish", None)
+            return outputs
+        outputs["panoptic_finish"] = finish
 
     def _panoptic_branch(self, panoptic_coords, panoptic_voxel_feats, bs, outputs, pruned=None):
         """ancestor pruning of the coarser levels, 48-channel projections, mask features, decoder (:516-581); fills
@@ -506,14 +516,12 @@ class NeuConNet(nn.Module):
         return sum(total) / len(total)
 
     @staticmethod
-    def prune_to_ancestors(panoptic_coords):
+    def prune_to_ancestors(panoptic_coords, n_dev=None):
         """models/neucon_network.py:516-542 (K17): keep the level-1 voxels that are floor(c/2)*2 of some
         level-2 voxel, and the level-0 voxels that are floor(c/4)*4 of one — a hash-grid membership
-        query instead of the reference's [N1, M, 4] broadcast compare."""
+        query instead of the reference's [N1, M, 4] broadcast compare.  n_dev: the device count of the live level-2 rows."""
         fine = panoptic_coords[2].contiguous()
-        dev = fine.device
-        g2 = SP.HashGrid(fine.shape[0], dev).build(fine, quantum=2)
-        keep1 = g2.query(panoptic_coords[1].contiguous()) >= 0
-        g4 = SP.HashGrid(fine.shape[0], dev).build(fine, quantum=4)
-        keep0 = g4.query(panoptic_coords[0].contiguous()) >= 0
+        grid = lambda quantum: SP.HashGrid(fine.shape[0], fine.device).build(fine, quantum=quantum, n_dev=n_dev)
+        keep1 = grid(2).query(panoptic_coords[1].contiguous()) >= 0
+        keep0 = grid(4).query(panoptic_coords[0].contiguous()) >= 0
         return keep1, keep0

@@ -248,7 +248,6 @@ class Occupancy_Initialization(nn.Module):
         coord_valid = res["coords"]
         parts = []
         start = 0
-        self.dense_checks = []   # (kept for callers that passed it on: a DenseMap defers its own off-grid check now, sparse.DenseMap)
         for b in range(bs):  # statistics of norm0 / norm4 are per batch element, as in the reference
             nb = res["n_valid_per_batch"][b]
             seg = slice(start, start + nb)

@@ -110,6 +110,15 @@ def test_prefetch_off(scene, default_run, monkeypatch):
     assert 3 * n <= (r2 - r1) - (r1 - r0) <= 4 * n, ((r1 - r0) / n, (r2 - r1) / n)
 
 
+def test_sparsify_on_torch_calls(scene, default_run, monkeypatch):
+    """neucon_network._FUSED_SPARSIFY off: every level's tail on the reference's sequence of torch calls (which also ends the
+    prefetch: nothing is queued behind a compaction) instead of eprecon_sparsify_async — bit-identical fragments"""
+    import eprecon_amd.neucon_network as NN
+    monkeypatch.setattr(NN, "_FUSED_SPARSIFY", False)
+    got = run_scene(scene)
+    assert_same_scene(default_run, got, exact=True)
+
+
 def test_spvcnn_issued_from_python(scene, default_run, monkeypatch):
     """EPRECON_SPVCNN_NATIVE=0: the body of every SPVCNN pass issued launch by launch from Python instead of by one library call
     (eprecon_spvcnn_forward_async): the same entry points with the same descriptors in the same order — bit-identical"""

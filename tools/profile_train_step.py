@@ -18,11 +18,11 @@ for _ in range(steps):
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / steps
 with torch.no_grad():
-    s.net.gru_fusion.scene_name = [None, None, None]
+    s.net.gru_fusion.new_scene()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        s.net.gru_fusion.scene_name = [None, None, None]
+        s.net.gru_fusion.new_scene()
         s.net(s.f1, s.f2, s.inputs, {})
     torch.cuda.synchronize()
     inf = (time.perf_counter() - t0) / steps
