@@ -203,6 +203,9 @@ SIGNATURES = {
     "eprecon_views_to_rows_async": (_i, [_vp, _vp]),
     "eprecon_prepare_views_async": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     "eprecon_depth_to_metres_async": (_i, [_vp, _i64, _f, _vp, _vp]),
+    "eprecon_grad_sqsum_async": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "eprecon_grad_norm_finish_async": (_i, [_vp, _i, _f, _vp, _vp]),
+    "eprecon_adam_update_async": (_i, [_vp, _vp, _i, _vp, _f, _f, _f, _f, _f, _vp, _f, _vp, _vp]),
 }
 
 # include/eprecon_hip.h: EPRECON_VIEWS_TILE_H (the output rows a workgroup of eprecon_prepare_views_async owns: the caller sizes
@@ -286,6 +289,21 @@ class BpCall(ctypes.Structure):
                 ("phase", ctypes.c_int32), ("out_feats", ctypes.c_void_p), ("out_mean", ctypes.c_void_p),
                 ("out_coords", ctypes.c_void_p), ("out_grid", ctypes.c_void_p), ("out_mask", ctypes.c_void_p),
                 ("rank", ctypes.c_void_p)]
+
+
+class AdamSegment(ctypes.Structure):
+    """include/eprecon_hip.h: eprecon_adam_segment"""
+    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
+                ("exp_avg_sq", ctypes.c_void_p)]
+
+
+class AdamChunk(ctypes.Structure):
+    """include/eprecon_hip.h: eprecon_adam_chunk"""
+    _fields_ = [("segment", ctypes.c_int32), ("start", ctypes.c_int32), ("count", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
+# include/eprecon_hip.h: EPRECON_ADAM_ALL_ALIGNED, EPRECON_ADAM_GRAD_ALIGNED
+ADAM_ALL_ALIGNED, ADAM_GRAD_ALIGNED = 1, 2
 
 
 class GtCropDesc(ctypes.Structure):

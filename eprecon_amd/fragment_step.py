@@ -450,8 +450,11 @@ class TrainStep:
 
     LW = (1.0, 0.8, 0.64, 1.2)       # config/train.yaml:44
 
-    def __init__(self, seed=0, device=None, height=480, width=640, lr=1e-4, rank=0, world=1, batch=1):
-        """batch: fragment windows per step and rank (consecutive windows of the scene; the reference trains at BATCH_SIZE 4,
+    def __init__(self, seed=0, device=None, height=480, width=640, lr=1e-4, rank=0, world=1, batch=1,
+                 optimizer="torch"):
+        """optimizer: "torch" — clip_grad_norm_ + torch.optim.Adam + repack_registered; "fused" — optim.FusedAdam, the same
+        step as this project's own launches.
+        batch: fragment windows per step and rank (consecutive windows of the scene; the reference trains at BATCH_SIZE 4,
         config/train.yaml:2 — every stage of the forward loops over the batch elements, the BatchNorms see them all)"""
         from .config import ModelCfg
         from .neucon_network import NeuConNet
@@ -479,7 +482,13 @@ class TrainStep:
             clear_packed_weights(self.net)
             self.model = DistributedDataParallel(self.net, device_ids=[self.device.index], output_device=self.device.index,
                                                  broadcast_buffers=False, find_unused_parameters=True)
-        self.optimizer = torch.optim.Adam(self.model.parameters(), lr=lr, betas=(0.9, 0.999))
+        assert optimizer in ("torch", "fused"), optimizer
+        if optimizer == "fused":
+            from .optim import FusedAdam
+            self.optimizer = FusedAdam(self.model.parameters(), lr=lr, betas=(0.9, 0.999))
+        else:
+            self.optimizer = torch.optim.Adam(self.model.parameters(), lr=lr, betas=(0.9, 0.999))
+        self.fused = optimizer == "fused"
         self.last = None
         self.steps = 0
         self.early_returns = 0      # steps whose forward returned before the finest level / the panoptic criterion
@@ -518,6 +527,10 @@ class TrainStep:
         else:
             self.voxels.append(int(outputs["coords"].shape[0]))
         loss_dict["total_loss"].backward()
+        if self.fused:
+            self.optimizer.clip_and_step(1.0)      # (ends with the repack)
+            self.last = {k: float(v.detach()) if torch.is_tensor(v) else float(v) for k, v in loss_dict.items()}
+            return self.last
         torch.nn.utils.clip_grad_norm_(self.model.parameters(), 1.0)
         self.optimizer.step()
         # every weight has changed: all operand-order copies rebuilt by ONE launch here instead of one per layer at its next use

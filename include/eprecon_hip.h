@@ -1367,6 +1367,45 @@ int eprecon_prepare_views_async(const uint8_t *frames, int n_views, int height, 
                                 int out_h, int out_w, float *out, void *stream);
 int eprecon_depth_to_metres_async(const uint16_t *depth_mm, int64_t n, float max_depth, float *out, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Optimiser step  (csrc/optim.hip: main.py:308-310, torch.nn.utils.clip_grad_norm_(parameters, 1.0) and
+ * torch.optim.Adam.step() over every trainable parameter, in two or three launches)
+ *
+ * A SEGMENT is one parameter's contiguous fp32 storage with its gradient and Adam moments.  The host cuts the segments
+ * into CHUNKS of one segment each (start and count in floats, start a multiple of the chunk length) and uploads both
+ * tables when a pointer or the membership changes; one workgroup works on one chunk.  flags: the float4 form is taken where
+ * the addresses it would use are 16-byte aligned (ALL: param, grad, exp_avg and exp_avg_sq at `start`; GRAD: grad alone,
+ * for the norm), the scalar form otherwise; a count that is no multiple of 4 ends in scalar elements.
+ *
+ * eprecon_grad_sqsum_async: partials f64[nchunks], partials[c] = sum of the squares of chunk c's gradient, accumulated in
+ *   double (every square exact) and reduced in a fixed order: no atomics, the same bits on every run.
+ * eprecon_grad_norm_finish_async: one workgroup sums the partials in a fixed order -> norm_coef f32[2] = {norm,
+ *   coef = min(1, max_norm / (norm + 1e-6))}, float arithmetic as clip_grad_norm_ has it; a NaN norm gives a NaN coef.
+ * eprecon_adam_update_async: for every element, with the segment's seg_scalars f32[nsegments][2] = {lr / bias_correction1,
+ *   sqrt(bias_correction2)} (the host forms them in double from the parameter's own step count):
+ *       g = coef * grad (+ weight_decay * p);  m += lerp_weight * (g - m);  v = beta2 * v + one_minus_beta2 * g * g;
+ *       p += -(lr / bias1) * (m / (sqrt(v) / sqrt(bias2) + eps))
+ *   — torch's non-amsgrad Adam.  coef: 1 when partials and norm_coef are NULL (no clipping); norm_coef[1] as the finish
+ *   launch left it when partials is NULL; with partials given, every workgroup sums them itself (the finish launch's order
+ *   and bits; none is needed then) and workgroup 0 stores norm_coef.  The gradients are read, never written: they stay
+ *   unclipped.
+ * EPRECON_EMPTY: nchunks == 0 (nothing launched).
+ * ------------------------------------------------------------------------------------------ */
+#define EPRECON_ADAM_ALL_ALIGNED 1
+#define EPRECON_ADAM_GRAD_ALIGNED 2
+typedef struct eprecon_adam_segment {
+    float *param; const float *grad; float *exp_avg; float *exp_avg_sq;
+} eprecon_adam_segment;
+typedef struct eprecon_adam_chunk {
+    int32_t segment; int32_t start; int32_t count; int32_t flags;
+} eprecon_adam_chunk;
+int eprecon_grad_sqsum_async(const eprecon_adam_segment *segs_dev, const eprecon_adam_chunk *chunks_dev, int nchunks,
+                             double *partials, void *stream);
+int eprecon_grad_norm_finish_async(const double *partials, int nchunks, float max_norm, float *norm_coef, void *stream);
+int eprecon_adam_update_async(const eprecon_adam_segment *segs_dev, const eprecon_adam_chunk *chunks_dev, int nchunks,
+                              const float *seg_scalars, float lerp_weight, float beta2, float one_minus_beta2, float eps,
+                              float weight_decay, const double *partials, float max_norm, float *norm_coef, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
