@@ -19,6 +19,8 @@
 // Pipeline: mc_count (per grid point: cut edges it owns along +x, +y, +z; per cell: triangle count) -> two scans ->
 // mc_emit (vertices with gradient normals and optional label lookups; faces through the owning grid point of each
 // edge, oriented so that the face normal agrees with the field gradient).  Output order is raster order: deterministic.
+// The winding of a face whose normal is perpendicular to the cell gradient within 2^-20 s (s: the magnitudes that enter
+// (u x w) . g, tests/mesh_ref.py) is unspecified; every other face is checked against the float64 witness there.
 #include <math.h>
 #include <string.h>
 

@@ -7,6 +7,9 @@ zero crossing; faces from a 256-case table generated from ONE rule (segments on 
 ambiguous faces, loops fanned).  PARITY UNPINNED against skimage for the face list; the mesh is pinned by its
 properties (watertight, on the level set) in tests/test_marching_cubes.py.  Written independently of the C++ generator
 (different data structures) so that comparing the two tables is a real check.
+
+Accepted winding differences: the winding of a face whose normal is perpendicular to the cell gradient within 2^-20 s
+is unspecified (s: the magnitudes that enter (u x w) . g, tests/mesh_ref.py); every other face is wound along the gradient.
 """
 import numpy as np
 

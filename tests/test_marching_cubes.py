@@ -77,6 +77,11 @@ def test_hip_mesh_equals_oracle(shape):
     r = np.clip(np.rint(ov).astype(int), 0, np.array(shape) - 1)               # utils.py:236-239
     assert np.array_equal(vs.cpu().numpy(), sem[r[:, 0], r[:, 1], r[:, 2]])
     assert np.array_equal(vi.cpu().numpy(), ins[r[:, 0], r[:, 1], r[:, 2]])
+    # the normals' direction and the winding, against the float64 witness (tests/mesh_ref.py)
+    import mesh_ref
+    res = mesh_ref.compare((verts.cpu().numpy(), faces.cpu().numpy(), n, vs.cpu().numpy(), vi.cpu().numpy()), vol, 0.0,
+                           labels=(sem, ins))
+    assert res["normal"] <= 1.0 and res["undecided"] == 0.0 and res["winding_differs"] == 0
 
 
 @pytest.mark.gpu
