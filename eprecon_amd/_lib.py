@@ -145,6 +145,9 @@ SIGNATURES = {
     "eprecon_render_visibility_async": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _f, _f, _f, _i, _vp, _i64, _vp, _sz, _vp]),
     "eprecon_render_resolve_async": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _c.c_int32, _vp, _vp,
                                           _c.c_int32, _vp, _vp, _c.c_double, _i, _i, _i, _vp, _vp]),
+    "eprecon_colorize_accumulate_async": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _vp, _i, _i, _vp, _i, _i, _f, _f, _f, _c.c_double,
+                                               _c.c_double, _vp, _vp, _vp]),
+    "eprecon_colorize_finish_async": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp, _vp]),
     "eprecon_depth_metrics_workspace_bytes": (_sz, [_i]),
     "eprecon_depth_metrics_async": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _sz, _vp]),
     "eprecon_point_bounds_async": (_i, [_vp, _i64, _vp, _vp, _vp]),

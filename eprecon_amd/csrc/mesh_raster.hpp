@@ -1,4 +1,5 @@
-// Triangle rasteriser shared by the depth render (mesh_eval.hip) and the visibility buffer (mesh_render.hip).
+// Triangle rasteriser shared by the depth render (mesh_eval.hip) and the visibility buffer (mesh_render.hip); its point and
+// triangle expressions (point_camera, project_point, tri_camera, tri_planes) also serve vertex colouring (mesh_colorize.hip).
 //
 // One thread per (triangle, view) in a 2D grid (y = view) transforms its triangle into the camera (fp64), culls it, and
 // sizes its pixel box.  A box of at most kSmallBox pixels is walked by that thread; a larger one goes to a queue that a
@@ -54,6 +55,22 @@ __device__ __forceinline__ double dot3(const double *a, const double *b) { retur
 
 __device__ __forceinline__ int clamp_pix(double v, int hi) { return (int)fmin(fmax(v, -1.0), (double)hi + 1.0); }
 
+// the f32 world point p, widened, in the camera frame of the world->camera 3x4 M
+__device__ __forceinline__ void point_camera(const double *M, const float *p, double q[3])
+{
+    const double x = p[0], y = p[1], z = p[2];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) q[r] = ((M[4 * r] * x + M[4 * r + 1] * y) + M[4 * r + 2] * z) + M[4 * r + 3];
+}
+
+// image point of the camera-frame point q under K (last row 0 0 1): the homogeneous coordinates times 1 / z
+__device__ __forceinline__ void project_point(const double *K, const double *q, double &px, double &py)
+{
+    const double iz = 1.0 / q[2];
+    px = ((K[0] * q[0] + K[1] * q[1]) + K[2] * q[2]) * iz;
+    py = ((K[3] * q[0] + K[4] * q[1]) + K[5] * q[2]) * iz;
+}
+
 // corners of triangle `tri` in the camera frame of `view`; false: a vertex index out of range (the face is never drawn)
 __device__ __forceinline__ bool tri_camera(const RenderParams &P, int view, int64_t tri, int32_t id[3], double v[3][3])
 {
@@ -63,11 +80,7 @@ __device__ __forceinline__ bool tri_camera(const RenderParams &P, int view, int6
     if (id[0] < 0 || id[1] < 0 || id[2] < 0 || id[0] >= P.n_verts || id[1] >= P.n_verts || id[2] >= P.n_verts) return false;
     const double *M = P.cams + 18 + 12 * (size_t)view;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double x = P.verts[3 * (size_t)id[k]], y = P.verts[3 * (size_t)id[k] + 1], z = P.verts[3 * (size_t)id[k] + 2];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) v[k][r] = ((M[4 * r] * x + M[4 * r + 1] * y) + M[4 * r + 2] * z) + M[4 * r + 3];
-    }
+    for (int k = 0; k < 3; ++k) point_camera(M, P.verts + 3 * (size_t)id[k], v[k]);
     return true;
 }
 
@@ -110,9 +123,8 @@ static __device__ bool tri_setup(const RenderParams &P, int view, int64_t tri, T
     const double pc = (double)P.pixel_center, zn = (double)P.znear;
     double umin = 1e300, umax = -1e300, vmin = 1e300, vmax = -1e300;
     auto add = [&](const double *q) {
-        const double iz = 1.0 / q[2];
-        const double px = ((K[0] * q[0] + K[1] * q[1]) + K[2] * q[2]) * iz;
-        const double py = ((K[3] * q[0] + K[4] * q[1]) + K[5] * q[2]) * iz;
+        double px, py;
+        project_point(K, q, px, py);
         umin = fmin(umin, px); umax = fmax(umax, px); vmin = fmin(vmin, py); vmax = fmax(vmax, py);
     };
 #pragma unroll

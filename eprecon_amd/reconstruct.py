@@ -1,7 +1,7 @@
 """Reconstruct scenes from disk — the reference's test loop (main.py:104-121, :376-405, :429-436) as a tool:
 
     python -m eprecon_amd.reconstruct --data_path DIR [--source_path DIR] [--mode test|val] [--ckpt FILE] --out DIR \\
-           [--scenes FILE] [--n_views 9] [--size 640 480] [--host-views]
+           [--scenes FILE] [--n_views 9] [--size 640 480] [--host-views] [--color]
 
 reads <data_path>/all_tsdf_<n_views>_1/fragments_<mode>.pkl (eprecon_amd.generate_gt writes it) and the frames it names
 (scannet.ScanNetDataset), and walks the fragments in file order, one per step: PrepareViews -> RandomTransformSpace (no
@@ -18,6 +18,9 @@ exercises the pipeline, its meshes mean nothing.
 --host-views prepares the views as the reference does (ResizeImage + ToTensor on the host) instead of PrepareViews on the
 device; the two give the same tensors bit for bit.  The frames of the next fragment are read and decoded on up to 9
 threads while the current fragment runs.
+
+--color (off by default) colours every saved scene from its key frames — the image_ids of its fragments — once the scene
+is written (eprecon_amd.colorize) and puts mesh_color_<scene>.ply beside the other meshes; no other file changes.
 """
 import argparse
 import os
@@ -59,6 +62,7 @@ def parse_args(argv=None):
     ap.add_argument("--size", default=[640, 480], type=int, nargs=2, metavar=("W", "H"), help="image size the network sees")
     ap.add_argument("--host-views", action="store_true", help="ResizeImage + ToTensor on the host instead of PrepareViews")
     ap.add_argument("--seed", default=0, type=int)
+    ap.add_argument("--color", action="store_true", help="also write mesh_color_<scene>.ply, coloured from the scene's key frames")
     return ap.parse_args(argv)
 
 
@@ -90,6 +94,18 @@ def calibrate(model, inputs):
     norm = [model.normalizer(img) for img in torch.unbind(inputs["imgs"], 1)]
     frag = (model.backbone2d.forward_views(norm), model.backbone_occ_pano.forward_views(norm), inputs)
     calibrate_occupancy_heads(model.neucon_net, [frag])
+
+
+def color_saved_scenes(outputs, saver, epoch, source_path, key_frames, voxel_size):
+    """--color: the scenes this step saved, coloured from the key frames of their fragments"""
+    from .colorize import write_colored_scene
+    save_path = "{}_fusion_eval_{}".format(saver.log_dir, epoch)
+    for name in outputs.get("scene_name", []):
+        npz = os.path.join(save_path, name.replace("/", "-") + ".npz")
+        if os.path.exists(npz):
+            path, mesh = write_colored_scene(npz, source_path, name, save_path, ids=sorted(set(key_frames.get(name, []))),
+                                             tolerance=voxel_size)
+            print(f"[reconstruct] {name}: {100.0 * float((mesh['vertex_seen'] > 0).mean()):.1f} % of the vertices coloured -> {path}")
 
 
 def main(argv=None):
@@ -139,6 +155,7 @@ def main(argv=None):
 
         pending = start(0)
         scene, count, read_s, prepare_s, t_scene = None, 0, 0.0, 0.0, time.perf_counter()
+        key_frames = {}
         for idx in range(n):
             done = [f.result() for f in pending]
             pending = start(idx + 1) if idx + 1 < n else None          # the lookahead: one fragment
@@ -159,6 +176,9 @@ def main(argv=None):
                 saver.keyframe_id = idx
                 outputs, _ = model(inputs, idx == n - 1, training=False)
             saver(outputs, inputs, epoch)
+            if args.color:
+                key_frames.setdefault(meta["scene"], []).extend(int(i) for i in meta["image_ids"])
+                color_saved_scenes(outputs, saver, epoch, dataset.source_path, key_frames, float(cfg.MODEL.VOXEL_SIZE))
             count += 1
         torch.cuda.synchronize(device)
         report(scene, count, time.perf_counter() - t_scene, read_s, prepare_s)

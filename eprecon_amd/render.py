@@ -167,6 +167,12 @@ def scene_mesh(npz_path, device=None):
     """<scene>.npz in either form SaveScene writes -> (verts f32[N,3] world, faces int32[M,3], semantic, instance int32[N])
     on the device: marching cubes of the TSDF at level 0 with the label volumes sampled at the vertices, as
     tsdf_panoptic2mesh does.  The sparse form's volumes are built on the device (TSDF default 1, ids default 0)."""
+    verts, faces, _, vsem, vins = scene_mesh_normals(npz_path, device)
+    return verts, faces, vsem, vins
+
+
+def scene_mesh_normals(npz_path, device=None):
+    """scene_mesh with marching cubes' normals -> (verts, faces, normals f32[N,3], semantic, instance)"""
     dev = torch.device(device if device is not None else "cuda")
     sem, ins, origin, voxel_size = _scene_volumes(npz_path, dev)
     with np.load(npz_path) as z:
@@ -178,8 +184,8 @@ def scene_mesh(npz_path, device=None):
             tsdf[c[:, 0], c[:, 1], c[:, 2]] = values
         else:
             tsdf = values
-    verts, faces, _, vsem, vins = marching_cubes(tsdf, 0.0, labels=(sem, ins))
-    return verts * voxel_size + torch.from_numpy(origin.reshape(1, 3)).to(dev), faces, vsem, vins
+    verts, faces, normals, vsem, vins = marching_cubes(tsdf, 0.0, labels=(sem, ins))
+    return verts * voxel_size + torch.from_numpy(origin.reshape(1, 3)).to(dev), faces, normals, vsem, vins
 
 
 def palette_colors(ids):

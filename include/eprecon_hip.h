@@ -946,6 +946,38 @@ int eprecon_render_resolve_async(const uint64_t *vis, const float *verts, int64_
                                  const uint8_t *colors, double ambient, int bg_red, int bg_green, int bg_blue,
                                  uint8_t *rgb_out, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Vertex colours from posed colour frames  (csrc/mesh_colorize.hip; the project's own rule)
+ *
+ * Accumulate  (one thread per vertex, the call's views looped in ascending order, no atomics)
+ *   verts f32[nv,3] (world), faces int32[nf,3].  cams f64[9 + 9 + 12 n_views] on the device: K_color (row-major 3x3, the
+ *   intrinsics of the frames), K_vis (the intrinsics of the visibility buffer), then per view the world->camera 3x4;
+ *   both K with the last row 0 0 1.  frames u8[n_views,hc,wc,3] (hc, wc >= 2), vis u64[n_views,hd,wd]: the
+ *   visibility buffer of THIS mesh from the same views (eprecon_render_visibility_async at K_vis).  Everything fp64,
+ *   sums associated (a x + b y) + c z.  Per vertex p and view, the pair is kept only if all of these hold:
+ *     q = w2c p,  z = q.z,  znear <= z <= zfar;
+ *     (u_d, v_d) = (K_vis q) * (1 / z), cd = floor(u_d - pixel_center + 0.5), rd likewise from v_d, inside the buffer;
+ *     the word at (rd, cd) is a hit: upper word < 0x7F800000 and its face index a drawable face (< nf, corners in
+ *     range: the tests of eprecon_render_resolve_async), and z <= D + tolerance with D the word's fp32 depth;
+ *     n = the plane normal (b-a) x (c-a) of that face in the camera frame, |n| > 0, cos = |n.q| / (|n| |q|) >= min_cos;
+ *     (u_c, v_c) = (K_color q) * (1 / z), x = u_c - pixel_center, y = v_c - pixel_center, 0 <= x <= wc-1, 0 <= y <= hc-1.
+ *   Then x0 = min(floor(x), wc-2), fx = x - x0, the same for y; per channel the bilinear value
+ *   (1-fy) ((1-fx) c00 + fx c01) + fy ((1-fx) c10 + fx c11) of the four bytes; w = cos / z^2;
+ *   acc f64[nv,4] += (w r, w g, w b, w), seen int32[nv] += 1.  acc and seen are the caller's state (zero before the
+ *   first call); each vertex's sums are one sequential chain over the views of a call and over calls, so the result
+ *   is bit-identical run to run and however the views are split into calls.  Argument rules return
+ *   EPRECON_ERR_ARG; nv == 0 or n_views == 0 is a no-op.  One launch per 64 views.
+ *
+ * Finish  (one thread per vertex)
+ *   rgb_out u8[n,3]: min(255, floor(acc_c / acc_w + 0.5)) where seen >= min_views and acc_w > 0, else the fallback bytes.
+ * ------------------------------------------------------------------------------------------ */
+int eprecon_colorize_accumulate_async(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, const double *cams,
+                                      int n_views, const uint8_t *frames, int hc, int wc, const uint64_t *vis, int hd, int wd,
+                                      float pixel_center, float znear, float zfar, double tolerance, double min_cos, double *acc,
+                                      int32_t *seen, void *stream);
+int eprecon_colorize_finish_async(const double *acc, const int32_t *seen, int64_t n, int min_views, int fallback_red,
+                                  int fallback_green, int fallback_blue, uint8_t *rgb_out, void *stream);
+
 /* Depth metrics (eval_depth of tools/evaluation_utils.py, batched): pred, trgt f32[n_frames, n_pix].  sums_out
  * f64[n_frames, 10] per frame, in a fixed order (run-to-run bit-identical): valid pixels (pred > 0, 0 < trgt < 10),
  * pixels with pred > 0, then over the valid pixels sum |p-t|/t, |p-t|, (p-t)^2/t, (p-t)^2, (ln p - ln t)^2 and the
