@@ -1,7 +1,7 @@
 """Reconstruct scenes from disk — the reference's test loop (main.py:104-121, :376-405, :429-436) as a tool:
 
     python -m eprecon_amd.reconstruct --data_path DIR [--source_path DIR] [--mode test|val] [--ckpt FILE] --out DIR \\
-           [--scenes FILE] [--n_views 9] [--size 640 480] [--host-views] [--color]
+           [--scenes FILE] [--n_views 9] [--size 640 480] [--host-views] [--color] [--clean N [--clean_segments N]]
 
 reads <data_path>/all_tsdf_<n_views>_1/fragments_<mode>.pkl (eprecon_amd.generate_gt writes it) and the frames it names
 (scannet.ScanNetDataset), and walks the fragments in file order, one per step: PrepareViews -> RandomTransformSpace (no
@@ -21,6 +21,10 @@ threads while the current fragment runs.
 
 --color (off by default) colours every saved scene from its key frames — the image_ids of its fragments — once the scene
 is written (eprecon_amd.colorize) and puts mesh_color_<scene>.ply beside the other meshes; no other file changes.
+
+--clean N (off by default) cleans every saved scene once it is written (eprecon_amd.clean_scene: connected pieces of the
+surface below N voxels are removed; with --clean_segments N, pieces of a segment below N voxels lose their ids) and puts
+the cleaned <scene>.npz and its three meshes into clean/ beside the saved scene; no other file changes.
 """
 import argparse
 import os
@@ -63,6 +67,10 @@ def parse_args(argv=None):
     ap.add_argument("--host-views", action="store_true", help="ResizeImage + ToTensor on the host instead of PrepareViews")
     ap.add_argument("--seed", default=0, type=int)
     ap.add_argument("--color", action="store_true", help="also write mesh_color_<scene>.ply, coloured from the scene's key frames")
+    ap.add_argument("--clean", type=int, metavar="N", help="also write clean/<scene>.npz and its meshes: the scene without "
+                                                            "its connected pieces of fewer than N voxels")
+    ap.add_argument("--clean_segments", default=0, type=int, metavar="N", help="with --clean: pieces of a segment of fewer "
+                                                                                "than N voxels lose their ids")
     return ap.parse_args(argv)
 
 
@@ -106,6 +114,19 @@ def color_saved_scenes(outputs, saver, epoch, source_path, key_frames, voxel_siz
             path, mesh = write_colored_scene(npz, source_path, name, save_path, ids=sorted(set(key_frames.get(name, []))),
                                              tolerance=voxel_size)
             print(f"[reconstruct] {name}: {100.0 * float((mesh['vertex_seen'] > 0).mean()):.1f} % of the vertices coloured -> {path}")
+
+
+def clean_saved_scenes(outputs, saver, epoch, min_voxels, min_segment_voxels):
+    """--clean: the scenes this step saved, cleaned into clean/ beside them"""
+    from .clean_scene import clean_scene, format_report
+    save_path = "{}_fusion_eval_{}".format(saver.log_dir, epoch)
+    for name in outputs.get("scene_name", []):
+        scene = name.replace("/", "-")
+        npz = os.path.join(save_path, scene + ".npz")
+        if os.path.exists(npz):
+            report = clean_scene(npz, os.path.join(save_path, "clean", scene + ".npz"), mesh=True, min_voxels=min_voxels,
+                                 min_segment_voxels=min_segment_voxels)
+            print(f"[reconstruct] {format_report(name, report)}")
 
 
 def main(argv=None):
@@ -179,6 +200,8 @@ def main(argv=None):
             if args.color:
                 key_frames.setdefault(meta["scene"], []).extend(int(i) for i in meta["image_ids"])
                 color_saved_scenes(outputs, saver, epoch, dataset.source_path, key_frames, float(cfg.MODEL.VOXEL_SIZE))
+            if args.clean is not None:
+                clean_saved_scenes(outputs, saver, epoch, args.clean, args.clean_segments)
             count += 1
         torch.cuda.synchronize(device)
         report(scene, count, time.perf_counter() - t_scene, read_s, prepare_s)

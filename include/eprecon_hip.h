@@ -272,6 +272,25 @@ int eprecon_unique_hierarchy_dn_async(const int32_t *coords, int64_t n_cap, cons
  */
 int eprecon_kernel_map_self_async(const void *table, uint32_t capacity, const int32_t *coords, int64_t n, int stride, int32_t *nbr,
                                   void *stream);
+
+/*
+ * Connected components of a sparse voxel set (csrc/components.hip; no counterpart in the reference, whose users cluster the
+ * finished mesh in open3d: the rule is DESIGN.md §5b, the caller eprecon_amd/clean_scene.py).
+ *   nbr           int32[27][n], the self map of n pairwise distinct rows (eprecon_kernel_map_self_async, stride 1)
+ *   keys          int32[n] or NULL (every key 0)
+ *   connectivity  6, 18 or 26: rows are adjacent when their coordinate difference d has d != 0, max |d_i| <= 1 and
+ *                 sum |d_i| <= 1, 2 or 3
+ * Rows i and j are linked iff they are adjacent, keys[i] == keys[j] and that key is >= 0; a row with a negative key links
+ * nothing and bridges nothing.  label[i] = the smallest row index of row i's component (label[i] <= i,
+ * label[label[i]] == label[i]), -1 for a row with a negative key: the same values on every run.
+ * Three launches (init, hook, flatten) whatever n and the components look like, no host read, no workgroup waits on another.
+ * status int32[1] (device): written by every call; 0 afterwards, or bit 0 / bit 1 when a bounded loop (a chain of more than n
+ * steps / a link retried more than n times) gave up — the labels mean nothing then, and the caller that reads it raises.
+ * workspace: eprecon_components_workspace_bytes(n) bytes, 4-byte aligned (the parent array).  n == 0 only clears status.
+ */
+size_t eprecon_components_workspace_bytes(int64_t n);
+int eprecon_components_async(const int32_t *nbr, int64_t n, const int32_t *keys, int connectivity, int32_t *label, int32_t *status,
+                             void *workspace, size_t workspace_bytes, void *stream);
 /* ------------------------------------------------------------------------------------------
  * Kernel maps and sparse convolution  (K5, K10, K11, K13)
  *
