@@ -7,6 +7,7 @@ operator raises.  torch is imported first so that the library binds to the same 
 import ctypes
 import os
 
+import numpy as np
 import torch  # noqa: F401  (must be loaded before the HIP library, see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -258,6 +259,25 @@ def check(rc, what):
         raise EpreconError(f"{what}: HIP error {-(rc + 1000)}")
     raise EpreconError(f"{what}: error {rc} "
                        "(-1 bad argument, -2 workspace too small, -3 unsupported size)")
+
+
+def need_device(*tensors):
+    """every argument a tensor on a GPU (or a torch.device of one), else EpreconError: the operators have no CPU fallback"""
+    for t in tensors:
+        dev = t if isinstance(t, torch.device) else t.device if isinstance(t, torch.Tensor) else None
+        if dev is None or dev.type != "cuda":
+            raise EpreconError("eprecon_amd operators need device tensors (no CPU fallback)")
+
+
+def to_device(a, dtype, dev):
+    """tensor or array -> a contiguous tensor of `dtype` on `dev`"""
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    return t.to(device=dev, dtype=dtype).contiguous()
+
+
+def host64(a):
+    """tensor or array -> float64 numpy on the host"""
+    return np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, np.float64)
 
 
 def ptr(t):

@@ -55,8 +55,7 @@ def _prep_feats(feats):
 
 def _prep_inputs(coords, origin, krcam, v, b, dev):
     """-> (coords int32[N, 4], origin f32[B, 3], krcam f32[V, B, 4, 4]), contiguous and on `dev`, for V views of B batch elements"""
-    if dev.type != "cuda":
-        raise _lib.EpreconError("eprecon_amd operators need device tensors (no CPU fallback)")
+    _lib.need_device(dev)
     coords_i = (coords if coords.dtype == torch.int32 else coords.to(torch.int32)).contiguous()
     origin_f = origin.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
     krcam_f = krcam.to(device=dev, dtype=torch.float32).contiguous()

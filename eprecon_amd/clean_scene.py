@@ -28,7 +28,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .evaluation import _need_device
+from ._lib import need_device, to_device
+from .scene_io import VOLUME_KEYS, raster_rows, read_scene, read_scene_list, scatter_volumes, write_scene
 from .sparse import HashGrid, check_hash_status
 
 CONNECTIVITIES = (6, 18, 26)
@@ -41,7 +42,7 @@ def components(coords, keys=None, connectivity=26):
     """coords int32[M,3] (pairwise distinct, |c| < 2^19 - 1), keys int32[M] or None -> label int32[M], all on the device.
     ValueError for duplicate rows, EpreconError for a CPU tensor, a coordinate out of the hash grid's range or a status
     word the kernels left set.  One host read (the three checks together); none, and no launch, for M == 0."""
-    _need_device(coords, *(() if keys is None else (keys,)))
+    need_device(coords, *(() if keys is None else (keys,)))
     if coords.dim() != 2 or coords.shape[1] != 3 or coords.dtype != torch.int32:
         raise ValueError(f"components: expected int32 coords [M,3], got {coords.dtype} {tuple(coords.shape)}")
     if int(connectivity) not in CONNECTIVITIES:
@@ -150,7 +151,7 @@ def clean_rows(coords, tsdf, semantic, instance, min_voxels=0, keep_largest=0, m
                connectivity=26):
     """coords int32[M,3], tsdf f32[M], semantic, instance int[M] on the device -> (coords, tsdf, semantic, instance, report):
     the kept rows in their order, their ids after the segment pass, and the counts of REPORT_KEYS as host ints"""
-    _need_device(coords, tsdf, semantic, instance)
+    need_device(coords, tsdf, semantic, instance)
     m = coords.shape[0]
     if tsdf.shape != (m,) or semantic.shape != (m,) or instance.shape != (m,):
         raise ValueError(f"clean_rows: {m} rows, values of shapes {tuple(tsdf.shape)}, {tuple(semantic.shape)}, {tuple(instance.shape)}")
@@ -160,16 +161,6 @@ def clean_rows(coords, tsdf, semantic, instance, min_voxels=0, keep_largest=0, m
 
 
 # ---------------------------------------------------------------------------------------------------------------- files
-
-def _dense_volumes(dims, coords, tsdf, semantic, instance, device):
-    c = torch.from_numpy(np.ascontiguousarray(coords, np.int64)).to(device)
-    vols = []
-    for values, fill, dtype in ((tsdf, 1.0, torch.float32), (semantic, 0, torch.int32), (instance, 0, torch.int32)):
-        vol = torch.full(dims, fill, dtype=dtype, device=device)
-        vol[c[:, 0], c[:, 1], c[:, 2]] = torch.from_numpy(np.ascontiguousarray(values)).to(device=device, dtype=dtype)
-        vols.append(vol)
-    return vols
-
 
 def clean_scene(npz_in, npz_out, mesh=False, device=None, **rule):
     """A scene file in either form SaveScene writes -> the cleaned file in the same form (dense: the same keys and dtypes,
@@ -182,61 +173,43 @@ def clean_scene(npz_in, npz_out, mesh=False, device=None, **rule):
     if unknown:
         raise TypeError(f"clean_scene: unknown keywords {sorted(unknown)}")
     dev = torch.device(device if device is not None else "cuda")
-    with np.load(npz_in) as z:
-        data = {k: z[k] for k in z.files}
-    sparse = "sparse_coords" in data
-    if sparse:
-        pre = "sparse_"
-        dims = tuple(int(d) for d in data["dims"])
-        file_coords = np.ascontiguousarray(data["sparse_coords"]).astype(np.int64).reshape(-1, 3)
-        order = np.lexsort((file_coords[:, 2], file_coords[:, 1], file_coords[:, 0]))           # raster order
-    elif all(k in data for k in ("tsdf", "semantic", "instance")) and data["tsdf"].ndim == 3:
-        pre = ""
-        dims = data["tsdf"].shape
-        file_coords = np.argwhere((data["tsdf"] != 1) | (data["semantic"] != 0) | (data["instance"] != 0))
-        order = np.arange(len(file_coords))
-    else:
+    scene = read_scene(npz_in, rest=True)
+    if scene.layout == "legacy":
         raise ValueError(f"{npz_in}: neither the dense nor the sparse form of a saved scene")
-    rows = file_coords[order]
-    pick = (lambda k: data[pre + k][order]) if sparse else (lambda k: data[k][rows[:, 0], rows[:, 1], rows[:, 2]])
-    to_dev = lambda a, dtype: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dtype)
-    keep, sem, ins, report = _clean(to_dev(rows, torch.int32), to_dev(pick("tsdf"), torch.float32), to_dev(pick("semantic"), torch.int64),
-                                    to_dev(pick("instance"), torch.int64), *(rule.get(k, d) for k, d in zip(RULE_KEYS, (0, 0, 0, False, 26))))
+    rows, tsdf, semantic, instance, order = raster_rows(scene)
+    keep, sem, ins, report = _clean(to_device(rows, torch.int32, dev), to_device(tsdf, torch.float32, dev), to_device(semantic, torch.int64, dev),
+                                    to_device(instance, torch.int64, dev), *(rule.get(k, d) for k, d in zip(RULE_KEYS, (0, 0, 0, False, 26))))
     report = _host_report(report)
     keep, sem, ins = keep.cpu().numpy(), sem.cpu().numpy(), ins.cpu().numpy()
-    out = dict(data)
-    if sparse:
+    if order is not None:
         kept = order[keep]                      # file positions of the kept rows, in raster order
         back = np.argsort(kept, kind="stable")  # ... and in the file's order
         idx = kept[back]
-        out["sparse_coords"], out["sparse_tsdf"] = data["sparse_coords"][idx], data["sparse_tsdf"][idx]
-        out["sparse_semantic"] = sem[back].astype(data["sparse_semantic"].dtype)
-        out["sparse_instance"] = ins[back].astype(data["sparse_instance"].dtype)
-        mesh_rows = (file_coords[idx], out["sparse_tsdf"], out["sparse_semantic"], out["sparse_instance"])
+        out = {"coords": scene.coords[idx], "tsdf": scene.arrays["tsdf"][idx], "semantic": sem[back].astype(scene.arrays["semantic"].dtype),
+               "instance": ins[back].astype(scene.arrays["instance"].dtype)}
+        mesh_rows = dict(out)
     else:
         gone, stay = rows[~keep], rows[keep]
-        out["tsdf"], out["semantic"], out["instance"] = data["tsdf"].copy(), data["semantic"].copy(), data["instance"].copy()
+        out = {k: scene.arrays[k].copy() for k in VOLUME_KEYS}
         out["tsdf"][gone[:, 0], gone[:, 1], gone[:, 2]] = 1
         for key, values in (("semantic", sem), ("instance", ins)):
             out[key][gone[:, 0], gone[:, 1], gone[:, 2]] = 0
             out[key][stay[:, 0], stay[:, 1], stay[:, 2]] = values.astype(out[key].dtype)
-        mesh_rows = (stay, out["tsdf"][stay[:, 0], stay[:, 1], stay[:, 2]], sem, ins)
+        mesh_rows = {"coords": stay, "tsdf": out["tsdf"][stay[:, 0], stay[:, 1], stay[:, 2]], "semantic": sem, "instance": ins}
     out_dir = os.path.dirname(os.path.abspath(npz_out))
     os.makedirs(out_dir, exist_ok=True)
-    with open(npz_out, "wb") as fh:              # (a file object: numpy appends no second .npz to the name)
-        np.savez_compressed(fh, **out)
+    write_scene(npz_out, **out, **scene.rest)
     report["path"] = npz_out
     if mesh:
         from .save_scene import export_ply, tsdf_panoptic2mesh
-        scene = os.path.splitext(os.path.basename(npz_out))[0]
-        tsdf_vol, sem_vol, ins_vol = _dense_volumes(tuple(int(d) for d in dims), *mesh_rows, dev)
-        if bool((tsdf_vol == 1).all()):
-            print(f"[eprecon_amd] warning: No valid data for scene {scene}")
+        scene_name = os.path.splitext(os.path.basename(npz_out))[0]
+        vols = scatter_volumes(scene.dims, mesh_rows.pop("coords"), mesh_rows, dev)
+        if bool((vols["tsdf"] == 1).all()):
+            print(f"[eprecon_amd] warning: No valid data for scene {scene_name}")
         else:
-            origin = torch.from_numpy(np.asarray(data["origin"], np.float32).reshape(3)).to(dev)
-            meshes = tsdf_panoptic2mesh(float(np.asarray(data["voxel_size"], np.float64)), origin, tsdf_vol, sem_vol, ins_vol)
+            meshes = tsdf_panoptic2mesh(scene.voxel_size, torch.from_numpy(scene.origin).to(dev), *(vols[k] for k in VOLUME_KEYS))
             for m, name in zip(meshes, ("{}.ply", "mesh_semantic_{}.ply", "mesh_instance_{}.ply")):
-                export_ply(m, os.path.join(out_dir, name.format(scene)))
+                export_ply(m, os.path.join(out_dir, name.format(scene_name)))
     return report
 
 
@@ -261,9 +234,8 @@ def parse_args(argv=None):
 
 
 def main(argv=None):
-    from .render import _read_scenes
     args = parse_args(argv)
-    for scene in _read_scenes(args.scenes):
+    for scene in read_scene_list(args.scenes):
         report = clean_scene(os.path.join(args.pred, scene + ".npz"), os.path.join(args.out, scene + ".npz"), mesh=args.mesh,
                              **{k: getattr(args, k) for k in RULE_KEYS})
         print(format_report(scene, report))

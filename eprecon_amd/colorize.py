@@ -26,8 +26,8 @@ import torch
 
 from . import _lib
 from . import render as RD
-from .evaluation import _host64
-from .save_scene import export_ply
+from ._lib import host64, need_device
+from .scene_io import export_ply, intrinsic, pose, pose_frame_ids, read_scene_list
 
 DEFAULT_FALLBACK = (153, 153, 153)       # resolve's grey
 DEFAULT_TOLERANCE = 0.04                 # one voxel of the default scene
@@ -40,7 +40,7 @@ class MeshColorizer:
 
     def __init__(self, verts, faces, vis_size=None, tolerance=DEFAULT_TOLERANCE, min_cos=DEFAULT_MIN_COS, znear=0.05,
                  zfar=100.0, pixel_center=0.5):
-        self.verts, self.faces = RD._mesh_tensors(verts, faces)
+        self.verts, self.faces = RD.mesh_tensors(verts, faces)
         self.vis_size = None if vis_size is None else (int(vis_size[0]), int(vis_size[1]))
         self.tolerance, self.min_cos = float(tolerance), float(min_cos)
         self.znear, self.zfar, self.pixel_center = float(znear), float(zfar), float(pixel_center)
@@ -55,7 +55,7 @@ class MeshColorizer:
         if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
             raise ValueError("integrate: expected uint8 frames [V,H,W,3]")
         v, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
-        p = _host64(poses).reshape(-1, 4, 4)
+        p = host64(poses).reshape(-1, 4, 4)
         if p.shape[0] != v:
             raise ValueError(f"integrate: {v} frames, {p.shape[0]} poses")
         if v == 0 or self.verts.shape[0] == 0:
@@ -64,7 +64,7 @@ class MeshColorizer:
             raise ValueError(f"integrate: frames of {h} x {w}; at least 2 x 2")
         dev = self.verts.device
         frames = frames.to(dev).contiguous()
-        k = _host64(K).reshape(3, 3)
+        k = host64(K).reshape(3, 3)
         if not np.array_equal(k[2], [0.0, 0.0, 1.0]):
             raise _lib.EpreconError("integrate: K must have the last row (0, 0, 1)")
         wd, hd = self.vis_size or RD.NATIVE_SIZE
@@ -76,9 +76,9 @@ class MeshColorizer:
 
     def accumulate(self, frames, vis, K, K_vis, poses):
         """the accumulate entry alone on a visibility buffer u64[V,Hd,Wd] of this mesh at K_vis (integrate() makes it)"""
-        RD._need_device(frames, vis)
-        p = _host64(poses).reshape(-1, 4, 4)
-        cams = torch.from_numpy(np.concatenate([_host64(K).reshape(9), _host64(K_vis).reshape(9),
+        need_device(frames, vis)
+        p = host64(poses).reshape(-1, 4, 4)
+        cams = torch.from_numpy(np.concatenate([host64(K).reshape(9), host64(K_vis).reshape(9),
                                                 np.linalg.inv(p)[:, :3, :4].ravel()])).to(self.verts.device)
         if frames.dtype != torch.uint8 or vis.dtype not in (torch.uint64, torch.int64) or vis.shape[0] != frames.shape[0] \
                 or p.shape[0] != frames.shape[0]:
@@ -110,13 +110,13 @@ def _split_rule(rule):
 
 
 def colorize_mesh(mesh, frames, K, poses, chunk=CHUNK, **rule):
-    """mesh: a mesh dict, a (verts, faces) pair or a .ply path (render._device_mesh) -> the mesh dict with vertex_colors
+    """mesh: a mesh dict, a (verts, faces) pair or a .ply path (render.device_mesh) -> the mesh dict with vertex_colors
     uint8[N,3] and vertex_seen int32[N] (numpy; vertices and faces too when the mesh was not a dict).  **rule:
     MeshColorizer's and colors()' keywords."""
-    verts, faces, extra = RD._device_mesh(mesh)
+    verts, faces, extra = RD.device_mesh(mesh)
     rule, finish = _split_rule(dict(rule))
     col = MeshColorizer(verts, faces, **rule)
-    p = _host64(poses).reshape(-1, 4, 4)
+    p = host64(poses).reshape(-1, 4, 4)
     if len(frames) != p.shape[0]:
         raise ValueError(f"colorize_mesh: {len(frames)} frames, {p.shape[0]} poses")
     for s in range(0, p.shape[0], max(int(chunk), 1)):
@@ -134,38 +134,30 @@ def scene_frames(data_path, scene, ids):
     (frames uint8[V,H,W,3], K f64[3,3], poses f64[V,4,4], the ids kept); frames whose pose is not finite are skipped"""
     from PIL import Image
     root = os.path.join(data_path, scene)
-    k = np.loadtxt(os.path.join(root, "intrinsic", "intrinsic_color.txt"))[:3, :3].astype(np.float64)
+    k = intrinsic(root, "color")
     frames, poses, kept = [], [], []
     for i in ids:
-        pose = np.loadtxt(os.path.join(root, "pose", f"pose_{int(i):d}.txt")).reshape(4, 4)
-        if not np.isfinite(pose).all():
+        p = pose(root, i)
+        if not np.isfinite(p).all():
             continue
         with Image.open(os.path.join(root, "color", f"color_{int(i):d}.jpg")) as im:
             frames.append(np.asarray(im.convert("RGB"), np.uint8))
-        poses.append(pose)
+        poses.append(p)
         kept.append(int(i))
     if not kept:
         return np.zeros((0, 2, 2, 3), np.uint8), k, np.zeros((0, 4, 4)), kept
     return np.stack(frames), k, np.array(poses, np.float64).reshape(-1, 4, 4), kept
 
 
-def _frame_ids(data_path, scene, every):
-    pose_dir = os.path.join(data_path, scene, "pose")
-    n = len([f for f in os.listdir(pose_dir) if f.startswith("pose_") and f.endswith(".txt")])
-    return list(range(0, n, max(int(every), 1)))
-
-
 def colorize_scene(npz_path, data_path, scene, every=10, ids=None, chunk=CHUNK, **rule):
     """a saved scene (either .npz form) coloured from its frames 0, every, 2 every, ... (or `ids`), read and integrated
     `chunk` at a time; the tolerance is the file's voxel_size unless given -> {vertices, faces, vertex_normals,
     vertex_colors, vertex_seen} (numpy): scene_mesh's geometry with marching cubes' normals"""
-    verts, faces, normals, _, _ = RD.scene_mesh_normals(npz_path)
-    with np.load(npz_path) as z:
-        voxel = float(z["voxel_size"])
+    verts, faces, normals, _, _, voxel = RD.scene_mesh_normals(npz_path)
     rule, finish = _split_rule(dict(rule))
     rule.setdefault("tolerance", voxel)
     col = MeshColorizer(verts, faces, **rule)
-    ids = _frame_ids(data_path, scene, every) if ids is None else [int(i) for i in ids]
+    ids = pose_frame_ids(os.path.join(data_path, scene), every) if ids is None else [int(i) for i in ids]
     step = max(int(chunk), 1)
     for s in range(0, len(ids), step):
         frames, k, poses, kept = scene_frames(data_path, scene, ids[s:s + step])
@@ -202,7 +194,7 @@ def parse_args(argv=None):
 def main(argv=None):
     args = parse_args(argv)
     out = args.out or args.pred
-    for scene in RD._read_scenes(args.scenes):
+    for scene in read_scene_list(args.scenes):
         path, mesh = write_colored_scene(os.path.join(args.pred, scene + ".npz"), args.data_path, scene, out, every=args.every,
                                          vis_size=tuple(args.vis_size), min_views=args.min_views)
         seen = mesh["vertex_seen"]

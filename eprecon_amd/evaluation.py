@@ -10,8 +10,8 @@ tools/evaluation_utils.py (pyrender + open3d there, neither available here), on 
 
     python -m eprecon_amd.evaluation --model DIR --data_path DIR --gt_path DIR [--max_depth 10] [--scenes ...]
 
-Device tensors are required (no CPU fallback); only read_ply and the metric assembly run on the host.  DESIGN.md §5 lists
-where this deviates from pyrender / open3d.
+Device tensors are required (no CPU fallback); only the file readers (scene_io.py) and the metric assembly run on the
+host.  DESIGN.md §5 lists where this deviates from pyrender / open3d.
 """
 import argparse
 import ctypes
@@ -23,7 +23,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .save_scene import export_ply, marching_cubes
+from ._lib import host64, need_device, to_device
+from .save_scene import marching_cubes, world_mesh
+from .scene_io import count_depth_frames, depth_metres, export_ply, intrinsic, load_mesh, pose, read_ply  # noqa: F401  (read_ply: for callers)
 from .tsdf_fusion import TSDFVolumeHIP
 
 DEPTH_KEYS = ["AbsRel", "AbsDiff", "SqRel", "RMSE", "LogRMSE", "r1", "r2", "r3", "complete"]
@@ -33,145 +35,8 @@ METRIC_KEYS = DEPTH_KEYS + MESH_KEYS          # tools/visualize_metrics.py key_n
 VOXEL_SIZE = 0.04          # re-fusion: voxel_length 4 cm, sdf_trunc 3 voxels (tools/evaluation.py:94-99)
 SDF_TRUNC_VOXELS = 3
 DEPTH_TRUNC = 5.0          # create_from_color_and_depth(depth_trunc=5.0)
-_QUEUE_CAP = 1 << 22       # large-triangle queue of the rasteriser (overflow is walked in place: slower, same result)
+QUEUE_CAP = 1 << 22        # large-triangle queue of the rasteriser (overflow is walked in place: slower, same result)
 _SLAB_CELLS = 1 << 24      # voxel down-sample: dense cells per pass
-
-
-def _need_device(*tensors):
-    for t in tensors:
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise _lib.EpreconError("eprecon_amd operators need device tensors (no CPU fallback)")
-
-
-def _host64(a):
-    return np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, np.float64)
-
-
-# ------------------------------------------------------------------------------------------------------ PLY (host)
-
-_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
-              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
-              "double": "f8", "float64": "f8"}
-
-
-def read_ply(path):
-    """PLY (binary little / big endian or ASCII) -> (vertices f32[N,3], faces int32[M,3]); polygons are fanned into
-    triangles, elements other than vertex / face are skipped.  numpy only."""
-    with open(path, "rb") as fh:
-        data = fh.read()
-    end = data.find(b"end_header")
-    if not data.startswith(b"ply") or end < 0:
-        raise ValueError(f"{path}: not a PLY file")
-    body = end + len(b"end_header")
-    body += 2 if data[body:body + 2] == b"\r\n" else 1
-    fmt, elements = None, []
-    for line in data[:end].decode("ascii", "replace").splitlines():
-        tok = line.split()
-        if not tok or tok[0] in ("ply", "comment", "obj_info"):
-            continue
-        if tok[0] == "format":
-            fmt = tok[1]
-        elif tok[0] == "element":
-            elements.append((tok[1], int(tok[2]), []))
-        elif tok[0] == "property":
-            if tok[1] == "list":
-                elements[-1][2].append((tok[4], _PLY_TYPES[tok[2]], _PLY_TYPES[tok[3]]))
-            else:
-                elements[-1][2].append((tok[2], _PLY_TYPES[tok[1]], None))
-    if fmt not in ("ascii", "binary_little_endian", "binary_big_endian"):
-        raise ValueError(f"{path}: unsupported PLY format {fmt}")
-    verts, faces = np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32)
-    if fmt == "ascii":
-        lines = data[body:].decode("ascii").split("\n")
-        li = 0
-        for name, count, props in elements:
-            rows = []
-            for _ in range(count):
-                while not lines[li].strip():
-                    li += 1
-                rows.append(lines[li].split())
-                li += 1
-            if name == "vertex":
-                names = [p[0] for p in props]
-                arr = np.array([[float(r[names.index(a)]) for a in "xyz"] for r in rows], np.float64).reshape(-1, 3)
-                verts = arr.astype(np.float32)
-            elif name == "face":
-                faces = _fan(_ascii_lists(rows, props))
-        return verts, faces
-    order = "<" if fmt == "binary_little_endian" else ">"
-    off = body
-    for name, count, props in elements:
-        if all(p[2] is None for p in props):
-            dt = np.dtype([(p[0], order + p[1]) for p in props])
-            rec = np.frombuffer(data, dt, count, off)
-            off += dt.itemsize * count
-            if name == "vertex":
-                verts = np.stack([rec[a] for a in "xyz"], 1).astype(np.float32)
-            continue
-        # an element with list properties: one structured read when every list holds three items (triangle meshes)
-        fields = []
-        for p in props:
-            fields += [(p[0], order + p[1])] if p[2] is None else [(p[0] + "_n", order + p[1]), (p[0], order + p[2], (3,))]
-        dt3 = np.dtype(fields)
-        if off + dt3.itemsize * count <= len(data):
-            rec = np.frombuffer(data, dt3, count, off)
-            if all((rec[p[0] + "_n"] == 3).all() for p in props if p[2]):
-                off += dt3.itemsize * count
-                if name == "face":
-                    key = [p[0] for p in props if p[2] and p[0] in ("vertex_indices", "vertex_index")]
-                    faces = np.ascontiguousarray(rec[key[0]], np.int32).reshape(-1, 3) if key else faces
-                continue
-        polys = []
-        for _ in range(count):
-            for p in props:
-                if p[2] is None:
-                    off += np.dtype(p[1]).itemsize
-                    continue
-                n = int(np.frombuffer(data, order + p[1], 1, off)[0])
-                off += np.dtype(p[1]).itemsize
-                items = np.frombuffer(data, order + p[2], n, off)
-                off += np.dtype(p[2]).itemsize * n
-                if p[0] in ("vertex_indices", "vertex_index"):
-                    polys.append(items.astype(np.int64))
-        if name == "face":
-            faces = _fan(polys)
-    return verts, faces
-
-
-def _ascii_lists(rows, props):
-    polys = []
-    for r in rows:
-        k = 0
-        for p in props:
-            if p[2] is None:
-                k += 1
-                continue
-            n = int(float(r[k]))
-            items = [int(float(x)) for x in r[k + 1:k + 1 + n]]
-            k += 1 + n
-            if p[0] in ("vertex_indices", "vertex_index"):
-                polys.append(np.array(items, np.int64))
-    return polys
-
-
-def _fan(polys):
-    tris = [np.stack([np.full(len(p) - 2, p[0]), p[1:-1], p[2:]], 1) for p in polys if len(p) >= 3]
-    return np.concatenate(tris).astype(np.int32) if tris else np.zeros((0, 3), np.int32)
-
-
-def _load_mesh(mesh_or_path):
-    """path / {vertices, faces} dict / (verts, faces) -> (verts f32[N,3], faces int32[M,3]) as numpy or tensors"""
-    if isinstance(mesh_or_path, (str, os.PathLike)):
-        return read_ply(mesh_or_path)
-    if isinstance(mesh_or_path, dict):
-        return mesh_or_path["vertices"], mesh_or_path["faces"]
-    return mesh_or_path
-
-
-def _to_dev(a, dtype, dev):
-    if isinstance(a, torch.Tensor):
-        return a.to(device=dev, dtype=dtype).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dtype).contiguous()
 
 
 # ------------------------------------------------------------------------------------------------------ rasteriser
@@ -181,20 +46,20 @@ def render_depth(verts, faces, K, poses, height, width, znear=0.05, zfar=100.0, 
     on the device: camera-frame z of the nearest surface in [znear, zfar], 0 where nothing is hit.  Pixel (r, c) samples
     the ray through (c + pixel_center, r + pixel_center): 0.5 is pyrender's (OpenGL) convention, 0 synthetic.render_depth's.
     cull_back: only faces with ((v1-v0) x (v2-v0)) . v0_cam < 0 are drawn (pyrender culls back faces by default)."""
-    _need_device(verts, faces)
+    need_device(verts, faces)
     lib = _lib.load()
     dev = verts.device
     verts = verts.to(torch.float32).contiguous()
     faces = faces.to(torch.int32).contiguous()
-    k = _host64(K).reshape(3, 3)
+    k = host64(K).reshape(3, 3)
     if not np.array_equal(k[2], [0.0, 0.0, 1.0]):
         raise _lib.EpreconError("render_depth: K must have the last row (0, 0, 1)")
-    p = _host64(poses).reshape(-1, 4, 4)
+    p = host64(poses).reshape(-1, 4, 4)
     w2c = np.linalg.inv(p)[:, :3, :4].reshape(-1, 12)
     cams = torch.from_numpy(np.concatenate([k.ravel(), np.linalg.inv(k).ravel(), w2c.ravel()])).to(dev)
     v = p.shape[0]
     out = torch.empty((v, height, width), dtype=torch.float32, device=dev)
-    cap = int(min(v * max(faces.shape[0], 1), _QUEUE_CAP))
+    cap = int(min(v * max(faces.shape[0], 1), QUEUE_CAP))
     ws = torch.empty(int(lib.eprecon_render_depth_workspace_bytes(cap)), dtype=torch.uint8, device=dev)
     _lib.check(lib.eprecon_render_depth_async(
         _lib.ptr(verts), verts.shape[0], _lib.ptr(faces), faces.shape[0], _lib.ptr(cams), v, int(height), int(width),
@@ -207,7 +72,7 @@ def render_depth(verts, faces, K, poses, height, width, znear=0.05, zfar=100.0, 
 
 def depth_sums(depth_pred, depth_trgt):
     """[V,H,W] device pair -> f64[V,10] per-frame sums (include/eprecon_hip.h: eprecon_depth_metrics_async), one reduction"""
-    _need_device(depth_pred, depth_trgt)
+    need_device(depth_pred, depth_trgt)
     lib = _lib.load()
     pred = depth_pred.to(torch.float32).contiguous()
     trgt = depth_trgt.to(device=pred.device, dtype=torch.float32).contiguous()
@@ -260,7 +125,7 @@ def average_depth_metrics(per_frame, n_frames):
 
 def point_bounds(points):
     """points f32[N,3] on the device (N >= 1) -> (min, max) float64[3] host arrays"""
-    _need_device(points)
+    need_device(points)
     lib = _lib.load()
     out = torch.empty(6 + 256 * 6, dtype=torch.float32, device=points.device)
     _lib.check(lib.eprecon_point_bounds_async(_lib.ptr(points), points.shape[0], _lib.ptr(out), _lib.ptr(out[6:]),
@@ -273,7 +138,7 @@ def voxel_down_sample(points, voxel):
     """open3d PointCloud.voxel_down_sample: min_bound = points.min(0) - voxel / 2, idx = floor((p - min_bound) / voxel)
     (fp64), out = mean of each occupied voxel's points (fp32), in voxel-key (x, y, z) order.  points f32[N,3] device.
     Dense cells in x slabs of <= 2^24: the cost grows with the extent of the cloud, not only with N."""
-    _need_device(points)
+    need_device(points)
     pts = points.to(torch.float32).contiguous()
     if pts.shape[0] == 0:
         return pts.reshape(0, 3).clone()
@@ -312,7 +177,7 @@ def nn_grid(lo, hi, n, cells_per_point=4, max_cells=1 << 26):
 def nn_correspondance(verts1, verts2):
     """tools/evaluation_utils.py nn_correspondance: for each point of verts2 the nearest point of verts1 (exact, fp64
     squared distances, smallest index on ties) -> (idx int64[n2], dist f32[n2]) on the device; empty when either is"""
-    _need_device(verts1, verts2)
+    need_device(verts1, verts2)
     dev = verts2.device
     v1 = verts1.to(torch.float32).contiguous()
     v2 = verts2.to(torch.float32).contiguous()
@@ -350,7 +215,7 @@ def mesh_metrics(dist1, dist2, threshold=0.05):
 def eval_mesh(verts_pred, verts_trgt, threshold=0.05, down_sample=0.02):
     """tools/evaluation_utils.py eval_mesh on device point sets (the meshes' vertices, as open3d's read_point_cloud
     of a .ply gives them)"""
-    _need_device(verts_pred, verts_trgt)
+    need_device(verts_pred, verts_trgt)
     p, t = verts_pred.to(torch.float32), verts_trgt.to(device=verts_pred.device, dtype=torch.float32)
     if down_sample:
         p, t = voxel_down_sample(p, down_sample), voxel_down_sample(t, down_sample)
@@ -380,16 +245,14 @@ class Refusion:
     def integrate(self, depths, K, poses):
         d = depths.clone()
         d[d > DEPTH_TRUNC] = 0.0
-        k = torch.as_tensor(np.asarray(_host64(K), np.float32)).reshape(1, 3, 3).expand(d.shape[0], 3, 3)
-        self.vol.integrate_views(d, k, torch.as_tensor(_host64(poses), dtype=torch.float32).reshape(-1, 4, 4))
+        k = torch.as_tensor(np.asarray(host64(K), np.float32)).reshape(1, 3, 3).expand(d.shape[0], 3, 3)
+        self.vol.integrate_views(d, k, torch.as_tensor(host64(poses), dtype=torch.float32).reshape(-1, 4, 4))
 
     def extract(self):
         """-> mesh dict {vertices, faces, vertex_normals} (host numpy, world metres)"""
         tsdf, weight = self.vol.get_volume()
         verts, faces, normals = marching_cubes(tsdf, 0.0, weight=weight)
-        origin = torch.as_tensor(self.origin, device=verts.device).reshape(1, 3)
-        return {"vertices": (verts * self.voxel_size + origin).cpu().numpy(), "faces": faces.cpu().numpy(),
-                "vertex_normals": normals.cpu().numpy()}
+        return world_mesh(self.voxel_size, self.origin, verts, faces, normals)
 
 
 # ------------------------------------------------------------------------------------------------------ driver
@@ -413,18 +276,18 @@ def evaluate_scene(mesh_or_path, frames, K, gt_mesh_or_path, out_dir=None, scene
     dev = torch.device(device) if device is not None else torch.device("cuda")
     if dev.type != "cuda":
         raise _lib.EpreconError("evaluate_scene needs a GPU (no CPU fallback)")
-    v_np, f_np = _load_mesh(mesh_or_path)
-    verts, faces = _to_dev(v_np, torch.float32, dev), _to_dev(f_np, torch.int32, dev)
-    k = _host64(K)[:3, :3]
+    v_np, f_np = load_mesh(mesh_or_path)
+    verts, faces = to_device(v_np, torch.float32, dev), to_device(f_np, torch.int32, dev)
+    k = host64(K)[:3, :3]
     fusion = Refusion(verts, device=dev) if verts.shape[0] else None
     per_frame, n_frames = [], 0
     for group in _chunks(frames, chunk):
         n_frames += len(group)
-        keep = [(p, d) for p, d in group if not np.isinf(_host64(p)[0, 0])]
+        keep = [(p, d) for p, d in group if not np.isinf(host64(p)[0, 0])]
         if not keep:
             continue
-        poses = np.stack([_host64(p) for p, _ in keep])
-        trgt = torch.stack([_to_dev(d, torch.float32, dev) for _, d in keep])
+        poses = np.stack([host64(p) for p, _ in keep])
+        trgt = torch.stack([to_device(d, torch.float32, dev) for _, d in keep])
         h, w = trgt.shape[-2:]
         pred = render_depth(verts, faces, k, poses, h, w)
         per_frame += eval_depth(pred, trgt)
@@ -434,8 +297,8 @@ def evaluate_scene(mesh_or_path, frames, K, gt_mesh_or_path, out_dir=None, scene
     trim = fusion.extract() if fusion is not None else {"vertices": np.zeros((0, 3), np.float32),
                                                         "faces": np.zeros((0, 3), np.int32),
                                                         "vertex_normals": np.zeros((0, 3), np.float32)}
-    gt_v, _ = _load_mesh(gt_mesh_or_path)
-    metrics.update(eval_mesh(_to_dev(trim["vertices"], torch.float32, dev), _to_dev(gt_v, torch.float32, dev)))
+    gt_v, _ = load_mesh(gt_mesh_or_path)
+    metrics.update(eval_mesh(to_device(trim["vertices"], torch.float32, dev), to_device(gt_v, torch.float32, dev)))
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
         name = scene.replace("/", "-")
@@ -448,13 +311,8 @@ def evaluate_scene(mesh_or_path, frames, K, gt_mesh_or_path, out_dir=None, scene
 def scannet_frames(scene_dir, max_depth=10.0):
     """(pose, depth) of every frame of a ScanNet-layout scene directory (tools/simple_loader.py): pose/pose_<i>.txt,
     depth/depth_<i>.png (16-bit millimetres), depth above max_depth zeroed; frames 0 .. (number of depth images) - 1"""
-    from PIL import Image
-    n = len([f for f in os.listdir(os.path.join(scene_dir, "depth")) if f.endswith(".png")])
-    for i in range(n):
-        pose = np.loadtxt(os.path.join(scene_dir, "pose", f"pose_{i:d}.txt"), delimiter=" ")
-        depth = np.asarray(Image.open(os.path.join(scene_dir, "depth", f"depth_{i:d}.png")), dtype=np.float32) / 1000.0
-        depth[depth > max_depth] = 0
-        yield pose, depth
+    for i in range(count_depth_frames(scene_dir)):
+        yield pose(scene_dir, i), depth_metres(os.path.join(scene_dir, "depth", f"depth_{i:d}.png"), max_depth)
 
 
 def visualize(fname):
@@ -486,7 +344,7 @@ def main(argv=None):
     results = {}
     for scene in scenes:
         sdir = os.path.join(args.data_path, scene)
-        k = np.loadtxt(os.path.join(sdir, "intrinsic", "intrinsic_depth.txt"), delimiter=" ")[:3, :3]
+        k = intrinsic(sdir, "depth")
         mesh = os.path.join(args.model, "%s.ply" % scene.replace("/", "-"))
         gt = os.path.join(args.gt_path, scene + "_vh_clean_2.ply")
         results[scene] = evaluate_scene(mesh, scannet_frames(sdir, args.max_depth), k, gt, out_dir=args.model, scene=scene,

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .scene_io import count_depth_frames, depth_metres, intrinsic, pose, read_scene_list
 from .tsdf_fusion import TSDFVolumeHIP
 
 MAX_BOUND_FRAMES = 200          # generate_gt.py:126-127
@@ -291,8 +292,7 @@ def generate_scene(scene, depths, cam_intr, poses, save_path, points=None, num_l
 def generate_pkl(save_path, split_file, split):
     """fragments_{split}.pkl = the fragments.pkl of the scenes the split file names, in sorted scene order
     (generate_gt.py:352-374)"""
-    with open(split_file) as f:
-        wanted = {line.strip() for line in f if line.strip()}
+    wanted = set(read_scene_list(split_file))
     fragments = []
     for scene in sorted(os.listdir(save_path)):
         if "scene" not in scene or scene not in wanted:
@@ -304,25 +304,13 @@ def generate_pkl(save_path, split_file, split):
     return fragments
 
 
-def read_depth(path, max_depth):
-    """a 16-bit PNG in millimetres -> f32[H,W] metres, values above max_depth zeroed (tools/simple_loader.py:44-47)"""
-    from PIL import Image
-    with Image.open(path) as im:
-        depth = np.asarray(im).astype(np.float32)
-    depth /= 1000.
-    depth[depth > max_depth] = 0
-    return depth
-
-
 def load_scannet_scene(data_path, scene, max_depth=3.0):
     """-> depths [f32[H,W]], cam_intr f64[3,3], poses [f64[4,4]] of an exported scene: pose/pose_{i}.txt,
     depth/depth_{i}.png, intrinsic/intrinsic_depth.txt (tools/simple_loader.py; the frame count is that of the depth maps)"""
     root = os.path.join(data_path, scene)
-    n_imgs = len([f for f in os.listdir(os.path.join(root, "depth")) if f.endswith(".png")])
-    cam_intr = np.loadtxt(os.path.join(root, "intrinsic", "intrinsic_depth.txt"), delimiter=" ")[:3, :3]
-    poses = [np.loadtxt(os.path.join(root, "pose", f"pose_{i}.txt"), delimiter=" ") for i in range(n_imgs)]
-    depths = [read_depth(os.path.join(root, "depth", f"depth_{i}.png"), max_depth) for i in range(n_imgs)]
-    return depths, cam_intr, poses
+    n_imgs = count_depth_frames(root)
+    depths = [depth_metres(os.path.join(root, "depth", f"depth_{i}.png"), max_depth) for i in range(n_imgs)]
+    return depths, intrinsic(root, "depth"), [pose(root, i) for i in range(n_imgs)]
 
 
 def load_panoptic_points(info_dir, scene):

@@ -1,6 +1,6 @@
 """Panoptic benchmark export — mirror of tools/generate_semantic_instance.py of the reference.
 
-A saved scene (origin, voxel_size, semantic and instance volumes: the .npz SaveScene writes, either form) gives every
+A saved scene (origin, voxel_size, semantic and instance volumes: the .npz SaveScene writes, any layout) gives every
 vertex of the scene's ScanNet mesh the labels of the nearest labelled voxel, and the files the ScanNet semantic and
 instance benchmarks accept are written:
 
@@ -23,7 +23,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .evaluation import _need_device, read_ply
+from ._lib import need_device
+from .scene_io import LABEL_KEYS, read_ply, read_scene_list, scene_volumes
 
 # tools/generate_semantic_instance.py:32 (class index of the network -> ScanNet label id; 0 = unlabelled, no site)
 SCANNET20_MAPPING = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16, 24, 28, 33, 34, 36, 39)
@@ -32,12 +33,12 @@ MAX_MAPPING = 256
 _ALL_SHELLS = (1 << 31) - 1
 
 
-def _c_i32(values):
+def c_i32(values):
     arr = (ctypes.c_int32 * len(values))(*[int(v) for v in values])
     return arr, ctypes.cast(arr, ctypes.c_void_p)
 
 
-def _mapping_list(mapping):
+def mapping_list(mapping):
     m = [int(v) for v in np.asarray(mapping).reshape(-1)]
     if not 1 <= len(m) <= MAX_MAPPING:
         raise ValueError(f"mapping: 1 .. {MAX_MAPPING} entries, got {len(m)}")
@@ -55,13 +56,13 @@ def brick_masks(semantic_i32, mapping):
     """semantic int32[X,Y,Z] on the device -> (masks int64[bricks] holding the 64-bit occupancy words, number of sites).
     The one host read of a transfer: the error flag and the site count.  ValueError on a class id outside the mapping."""
     lib = _lib.load()
-    m = _mapping_list(mapping)
+    m = mapping_list(mapping)
     dims = tuple(semantic_i32.shape)
     n_bricks = int(np.prod([(d + 3) // 4 for d in dims]))
     dev = semantic_i32.device
     masks = torch.empty(n_bricks, dtype=torch.int64, device=dev)
     status = torch.empty(2, dtype=torch.int32, device=dev)
-    (_d, dims_p), (_m, map_p) = _c_i32(dims), _c_i32(m)
+    (_d, dims_p), (_m, map_p) = c_i32(dims), c_i32(m)
     _lib.check(lib.eprecon_label_bricks_async(_lib.ptr(semantic_i32), dims_p, map_p, len(m), _lib.ptr(masks), _lib.ptr(status),
                                               _lib.current_stream()), "eprecon_label_bricks_async")
     bad, n_sites = _lib.read_counts(status)
@@ -77,9 +78,9 @@ def _near_shells(near_shells):
     return {"0": max(int(near_shells), 0), "1": -1, "2": _ALL_SHELLS}[path]
 
 
-def _query(masks, sem, ins, origin, voxel_size, vertices, mapping, near_shells):
+def query_labels(masks, sem, ins, origin, voxel_size, vertices, mapping, near_shells):
     lib = _lib.load()
-    m = _mapping_list(mapping)
+    m = mapping_list(mapping)
     dev = sem.device
     q = vertices.to(torch.float32).contiguous()
     if q.dim() != 2 or q.shape[1] != 3:
@@ -93,7 +94,7 @@ def _query(masks, sem, ins, origin, voxel_size, vertices, mapping, near_shells):
     voxel_size = float(np.asarray(voxel_size, np.float64))
     if not voxel_size > 0.0:
         raise ValueError(f"voxel_size must be positive, got {voxel_size}")
-    (_d, dims_p), (_m, map_p) = _c_i32(tuple(sem.shape)), _c_i32(m)
+    (_d, dims_p), (_m, map_p) = c_i32(tuple(sem.shape)), c_i32(m)
     origin_c = (ctypes.c_float * 3)(*origin.tolist())
     ws = _lib.workspace(int(lib.eprecon_label_transfer_workspace_bytes(dims_p, n)), dev)
     _lib.check(lib.eprecon_label_transfer_async(
@@ -108,19 +109,19 @@ def transfer_labels(semantic_vol, instance_vol, origin, voxel_size, vertices, ma
     vertices [N,3] on the device; origin (3 values, taken as float32 like the file's) and voxel_size (float64) on the
     host.  -> {semantic int32[N] (mapped id of the nearest labelled voxel), instance int32[N], index int32[N] (its linear
     cell index (x * Y + y) * Z + z), dist f32[N]} on the device; with no labelled voxel: 0, 0, -1, +inf."""
-    _need_device(semantic_vol, instance_vol, vertices)
+    need_device(semantic_vol, instance_vol, vertices)
     sem, ins = _label_volume(semantic_vol), _label_volume(instance_vol)
     if sem.shape != ins.shape:
         raise ValueError(f"semantic {tuple(sem.shape)} and instance {tuple(ins.shape)} volumes differ in shape")
     masks, _ = brick_masks(sem, mapping)
-    return _query(masks, sem, ins, origin, voxel_size, vertices, mapping, near_shells)
+    return query_labels(masks, sem, ins, origin, voxel_size, vertices, mapping, near_shells)
 
 
 def instance_table(mapped_semantic, mapped_instance):
     """:62-77 -> (ids ascending, class id per id, vertex count per id), int32 device tensors.  The class of an instance is
     the most frequent mapped class among its vertices; among equally frequent ones the class of the earliest vertex
     (Counter(...).most_common(1) in CPython)."""
-    _need_device(mapped_semantic, mapped_instance)
+    need_device(mapped_semantic, mapped_instance)
     lib = _lib.load()
     sem = mapped_semantic.to(torch.int32).contiguous().reshape(-1)
     ins = mapped_instance.to(torch.int32).contiguous().reshape(-1)
@@ -178,37 +179,18 @@ def write_submission(out_dir, scene, mapped_semantic, mapped_instance, ids, clas
     return written
 
 
-def _scene_volumes(path, device):
-    """<scene>.npz in either form SaveScene writes -> (semantic, instance int32[X,Y,Z] on the device, origin, voxel_size).
-    The sparse form's volumes are built on the device from the rows (ids default 0)."""
-    z = np.load(path)
-    prefix = "sparse_" if "sparse_coords" in z.files else ("" if "coords" in z.files and "dims" in z.files and
-                                                           z["semantic"].ndim == 1 else None)
-    if prefix is None:
-        vols = [torch.from_numpy(np.ascontiguousarray(z[k]).astype(np.int32)).to(device) for k in ("semantic", "instance")]
-    else:
-        dims = tuple(int(d) for d in z["dims"])
-        c = torch.from_numpy(z[prefix + "coords"].astype(np.int64)).to(device)
-        vols = []
-        for k in ("semantic", "instance"):
-            vol = torch.zeros(dims, dtype=torch.int32, device=device)
-            vol[c[:, 0], c[:, 1], c[:, 2]] = torch.from_numpy(z[prefix + k].astype(np.int32)).to(device)
-            vols.append(vol)
-    return vols[0], vols[1], np.asarray(z["origin"], np.float32).reshape(3), float(np.asarray(z["voxel_size"], np.float64))
-
-
 def generate_semantic_instance(scene_name, pred_dir, ply_dir, out_dir=".", device=None, mapping=SCANNET20_MAPPING):
     """the reference's function of the same name with its two hard-wired directories as arguments: <pred_dir>/<scene>.npz,
     <ply_dir>/<scene>_vh_clean_2.ply -> the three kinds of file under out_dir.  -> {n_vertices, n_instances, files}, or
     None (nothing written, a warning printed) when the scene has no labelled voxel (the reference crashes there)."""
     device = torch.device(device if device is not None else "cuda")
-    sem, ins, origin, voxel_size = _scene_volumes(os.path.join(pred_dir, scene_name + ".npz"), device)
+    sem, ins, origin, voxel_size = scene_volumes(os.path.join(pred_dir, scene_name + ".npz"), device, LABEL_KEYS)
     masks, n_sites = brick_masks(sem, mapping)
     if n_sites == 0:
         print(f"[eprecon_amd] warning: No labelled voxel for scene {scene_name}")
         return None
     verts, _ = read_ply(os.path.join(ply_dir, scene_name + "_vh_clean_2.ply"))
-    out = _query(masks, sem, ins, origin, voxel_size, torch.from_numpy(verts).to(device), mapping, 2)
+    out = query_labels(masks, sem, ins, origin, voxel_size, torch.from_numpy(verts).to(device), mapping, 2)
     ids, class_ids, _ = instance_table(out["semantic"], out["instance"])
     files = write_submission(out_dir, scene_name, out["semantic"], out["instance"], ids, class_ids)
     return {"n_vertices": int(verts.shape[0]), "n_instances": int(ids.numel()), "files": files}
@@ -221,9 +203,7 @@ def main(argv=None):
     ap.add_argument("--scenes", required=True, help="text file, one scene name per line")
     ap.add_argument("--out", default=".", help="where semantic/ and instance/ are written (default: here)")
     args = ap.parse_args(argv)
-    with open(args.scenes, "r", encoding="utf-8") as fh:
-        scenes = [line.strip() for line in fh if line.strip()]
-    for scene in scenes:
+    for scene in read_scene_list(args.scenes):
         print(scene)
         generate_semantic_instance(scene, args.pred, args.ply, args.out)
     return 0

@@ -33,9 +33,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .evaluation import _need_device, read_ply
+from ._lib import need_device
 from .generate_gt import load_panoptic_points
-from .generate_semantic_instance import SCANNET20_MAPPING, _c_i32, _mapping_list, _query, _scene_volumes, brick_masks
+from .generate_semantic_instance import SCANNET20_MAPPING, brick_masks, c_i32, mapping_list, query_labels
+from .scene_io import LABEL_KEYS, read_ply, read_scene_list, scene_volumes
 from .scene_fusion import STUFF_IDS
 
 VALID_CLASSES = SCANNET20_MAPPING[1:]      # models/criterion.py:112
@@ -47,14 +48,14 @@ _KEY_SHIFT, _INS_BIAS = 32, 1 << 31
 
 def _segment_table(semantic, instance, mapping, stuff_ids, valid_classes, absent_zero):
     """-> (rank, classes, keys, bad): segment_table plus a device flag (or None): a class index outside the mapping"""
-    _need_device(semantic, instance)
+    need_device(semantic, instance)
     if semantic.shape != instance.shape:
         raise ValueError(f"semantic {tuple(semantic.shape)} and instance {tuple(instance.shape)} differ in shape")
     dev = semantic.device
     sem, ins = semantic.to(torch.int64), instance.to(torch.int32).to(torch.int64)
     bad = None
     if mapping is not None:
-        m = torch.tensor(_mapping_list(mapping), dtype=torch.int64, device=dev)
+        m = torch.tensor(mapping_list(mapping), dtype=torch.int64, device=dev)
         out = (sem < 0) | (sem >= m.numel())
         sem = torch.where(out, torch.zeros_like(sem), m[sem.clamp(0, m.numel() - 1)])
         bad = out.any()
@@ -82,7 +83,7 @@ def segment_table(semantic, instance, mapping=None, stuff_ids=STUFF_IDS, valid_c
     rank -1.  ValueError for a class index outside the mapping (one host read, only with a mapping)."""
     rank, classes, keys, bad = _segment_table(semantic, instance, mapping, stuff_ids, valid_classes, absent_zero)
     if bad is not None and _lib.read_counts(bad.to(torch.int32))[0]:
-        raise ValueError(f"semantic values outside [0, {len(_mapping_list(mapping))})")
+        raise ValueError(f"semantic values outside [0, {len(mapping_list(mapping))})")
     return rank, classes, keys
 
 
@@ -104,7 +105,7 @@ def _table_buffers(n_pred, n_gt, dev):
 
 
 def _launch_pair_counts(pred_rank, gt_rank, n_pred, n_gt):
-    _need_device(pred_rank, gt_rank)
+    need_device(pred_rank, gt_rank)
     lib = _lib.load()
     p, g = (t.to(torch.int32).contiguous().reshape(-1) for t in (pred_rank, gt_rank))
     if p.numel() != g.numel():
@@ -150,7 +151,7 @@ def _lattice(dims_p, origin_p, vs_p, dims_g, origin_g, vs_g):
 
 
 def _launch_voxel_pair_counts(pred_rank, origin_p, vs_p, gt_rank, gt_tsdf, origin_g, vs_g, gt_surface, n_pred, n_gt):
-    _need_device(pred_rank, gt_rank, gt_tsdf)
+    need_device(pred_rank, gt_rank, gt_tsdf)
     lib = _lib.load()
     p, g = pred_rank.to(torch.int32).contiguous(), gt_rank.to(torch.int32).contiguous()
     t = gt_tsdf.to(torch.float32).contiguous()
@@ -164,7 +165,7 @@ def _launch_voxel_pair_counts(pred_rank, origin_p, vs_p, gt_rank, gt_tsdf, origi
     if int(np.prod(dims, dtype=np.int64)) >= 1 << 31:
         raise ValueError(f"a site lattice of {dims} cells (2^31 or more) is unsupported")
     counts, status = _table_buffers(n_pred, n_gt, p.device)
-    keep = [_c_i32(v) for v in (tuple(p.shape), tuple(g.shape), lo, dims)]
+    keep = [c_i32(v) for v in (tuple(p.shape), tuple(g.shape), lo, dims)]
     o_p, o_g = (ctypes.c_float * 3)(*origin_p.tolist()), (ctypes.c_float * 3)(*origin_g.tolist())
     _lib.check(lib.eprecon_voxel_pair_count_async(
         _lib.ptr(p), _lib.ptr(g), _lib.ptr(t), keep[0][1], keep[1][1], ctypes.cast(o_p, ctypes.c_void_p),
@@ -340,7 +341,7 @@ def score_sites(pred_sem, pred_ins, gt_sem, gt_ins, mapping=SCANNET20_MAPPING, t
                 valid_classes=VALID_CLASSES):
     """Labels of N sites on the device -> SceneTables.  pred_sem: class indices taken through `mapping` (None: ids already);
     0 = no prediction.  gt_sem: ScanNet ids; a class outside valid_classes (0 included) is void.  One host read."""
-    _need_device(pred_sem, pred_ins, gt_sem, gt_ins)
+    need_device(pred_sem, pred_ins, gt_sem, gt_ins)
     if pred_sem.numel() != gt_sem.numel():
         raise ValueError(f"{pred_sem.numel()} predicted and {gt_sem.numel()} ground-truth sites")
     p_rank, p_keys, bad = _pred_table(pred_sem.reshape(-1), pred_ins.reshape(-1), mapping, stuff_ids, valid_classes)
@@ -354,7 +355,7 @@ def score_volumes(pred_sem, pred_ins, pred_origin, pred_voxel, gt_tsdf, gt_sem, 
     """The voxel domain on device volumes [X,Y,Z]; origins are taken as float32 like the files', voxel sizes as float64.
     The sites are the cells of the prediction's lattice over the union of both boxes; ground truth is present where
     |tsdf| < gt_surface (compared in float32).  One host read."""
-    _need_device(pred_sem, pred_ins, gt_tsdf, gt_sem, gt_ins)
+    need_device(pred_sem, pred_ins, gt_tsdf, gt_sem, gt_ins)
     if gt_sem.shape != gt_tsdf.shape or gt_ins.shape != gt_tsdf.shape:
         raise ValueError(f"ground-truth volumes differ in shape: {tuple(gt_tsdf.shape)}, {tuple(gt_sem.shape)}, {tuple(gt_ins.shape)}")
     p_rank, p_keys, bad = _pred_table(pred_sem, pred_ins, mapping, stuff_ids, valid_classes)
@@ -377,12 +378,12 @@ def score_vertices(pred_npz, info_dir, scene, mapping=SCANNET20_MAPPING, thresho
     `pred_npz` at those vertices.  A scene with no labelled voxel scores as all-FN, with a warning.  Two host reads: the
     transfer's own (class range, site count) and the tables."""
     device = torch.device(device if device is not None else "cuda")
-    sem, ins, origin, voxel_size = _scene_volumes(pred_npz, device)
+    sem, ins, origin, voxel_size = scene_volumes(pred_npz, device, LABEL_KEYS)
     verts, gt_sem, gt_ins = load_panoptic_points(info_dir, scene)
     masks, n_sites = brick_masks(sem, mapping)
     if n_sites == 0:
         _warn_empty(scene)
-    out = _query(masks, sem, ins, origin, voxel_size, torch.from_numpy(np.ascontiguousarray(verts, np.float32)).to(device), mapping, 2)
+    out = query_labels(masks, sem, ins, origin, voxel_size, torch.from_numpy(np.ascontiguousarray(verts, np.float32)).to(device), mapping, 2)
     to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).astype(np.int64).reshape(-1)).to(device)
     return score_sites(out["semantic"], out["instance"], to_dev(gt_sem), to_dev(gt_ins), None, threshold, stuff_ids, valid_classes)
 
@@ -398,12 +399,12 @@ def score_voxels(pred_npz, gt_scene_dir, gt_surface=1.0, mapping=SCANNET20_MAPPI
     full_tsdf_layer0.npz, full_semantic_layer_interpolate0.npz, full_instance_layer_interpolate0.npz.  ValueError when
     the two voxel sizes differ by more than 1e-9 relative or the lattice has 2^31 sites or more."""
     device = torch.device(device if device is not None else "cuda")
-    sem, ins, origin, voxel_size = _scene_volumes(pred_npz, device)
+    sem, ins, origin, voxel_size = scene_volumes(pred_npz, device, LABEL_KEYS)
     with open(os.path.join(gt_scene_dir, "tsdf_info.pkl"), "rb") as fh:
         info = pickle.load(fh)
     tsdf = torch.from_numpy(np.ascontiguousarray(_arr0(os.path.join(gt_scene_dir, "full_tsdf_layer0.npz")), np.float32)).to(device)
     gt_sem, gt_ins = (torch.from_numpy(np.ascontiguousarray(_arr0(os.path.join(gt_scene_dir, f"full_{k}_layer_interpolate0.npz")))
-                                       .astype(np.int32)).to(device) for k in ("semantic", "instance"))
+                                       .astype(np.int32)).to(device) for k in LABEL_KEYS)
     tables = score_volumes(sem, ins, origin, voxel_size, tsdf, gt_sem, gt_ins, np.asarray(info["vol_origin"], np.float32).reshape(3),
                            float(info["voxel_size"]), gt_surface, mapping, threshold, stuff_ids, valid_classes)
     if tables.pred_classes.size == 0:
@@ -483,10 +484,8 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    with open(args.scenes, "r", encoding="utf-8") as fh:
-        scenes = [line.strip() for line in fh if line.strip()]
     score = PanopticScore()
-    for scene in scenes:
+    for scene in read_scene_list(args.scenes):
         npz = os.path.join(args.pred, scene + ".npz")
         if args.views is not None:
             from .render import scene_views

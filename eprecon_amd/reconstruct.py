@@ -38,6 +38,7 @@ from . import transforms as T
 from .config import ModelCfg
 from .save_scene import SaveScene
 from .scannet import ScanNetDataset
+from .scene_io import read_scene_list
 
 MAX_READERS = 9       # one per view of a fragment; never sized from the machine
 
@@ -141,8 +142,7 @@ def main(argv=None):
                              args.n_views, len(cfg.MODEL.THRESHOLDS) - 1, source_path=args.source_path,
                              raw=not args.host_views, device=device)
     if args.scenes:
-        with open(args.scenes, "r", encoding="utf-8") as fh:
-            wanted = {line.strip() for line in fh if line.strip()}
+        wanted = set(read_scene_list(args.scenes))
         dataset.metas = [m for m in dataset.metas if m["scene"] in wanted]
     n = len(dataset)
     if n == 0:

@@ -22,9 +22,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .evaluation import _QUEUE_CAP, _host64, _load_mesh, _need_device, _to_dev
-from .generate_semantic_instance import _scene_volumes
+from ._lib import host64, need_device, to_device
+from .evaluation import QUEUE_CAP
 from .save_scene import COLOR_PALETTE, marching_cubes
+from .scene_io import intrinsic, load_mesh, pose, pose_frame_ids, read_scene_list, scene_volumes
 
 DEFAULT_AMBIENT = 0.3                    # the reference's ambient_light
 DEFAULT_BACKGROUND = (255, 255, 255)     # the reference's bg_color
@@ -34,18 +35,18 @@ INF_BITS = 0x7F800000                    # upper word of a visibility entry at o
 
 
 def _cams(K, poses, dev, what):
-    k = _host64(K).reshape(3, 3)
+    k = host64(K).reshape(3, 3)
     if not np.array_equal(k[2], [0.0, 0.0, 1.0]):
         raise _lib.EpreconError(f"{what}: K must have the last row (0, 0, 1)")
-    p = _host64(poses).reshape(-1, 4, 4)
+    p = host64(poses).reshape(-1, 4, 4)
     if p.shape[0] < 1:
         raise ValueError(f"{what}: no pose")
     w2c = np.linalg.inv(p)[:, :3, :4].reshape(-1, 12)
     return torch.from_numpy(np.concatenate([k.ravel(), np.linalg.inv(k).ravel(), w2c.ravel()])).to(dev), p.shape[0]
 
 
-def _mesh_tensors(verts, faces):
-    _need_device(verts, faces)
+def mesh_tensors(verts, faces):
+    need_device(verts, faces)
     verts, faces = verts.to(torch.float32).contiguous(), faces.to(torch.int32).contiguous()
     if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
         raise ValueError(f"expected verts [N,3] and faces [M,3], got {tuple(verts.shape)} and {tuple(faces.shape)}")
@@ -58,12 +59,12 @@ def visibility(verts, faces, K, poses, height, width, znear=0.05, zfar=100.0, cu
     device (torch.uint64): (fp32 depth bits << 32) | index of the nearest face drawn at that pixel, all-ones where none
     is.  The arguments are evaluation.render_depth's, and the upper word is its result bit for bit (+inf bits or above
     instead of 0 where nothing is hit); at equal depth bits the smallest face index wins; run-to-run bit-identical."""
-    verts, faces = _mesh_tensors(verts, faces)
+    verts, faces = mesh_tensors(verts, faces)
     lib = _lib.load()
     dev = verts.device
     cams, v = _cams(K, poses, dev, "visibility")
     out = torch.empty((v, int(height), int(width)), dtype=torch.uint64, device=dev)
-    cap = int(min(v * max(faces.shape[0], 1), _QUEUE_CAP)) if queue_capacity is None else int(queue_capacity)
+    cap = int(min(v * max(faces.shape[0], 1), QUEUE_CAP)) if queue_capacity is None else int(queue_capacity)
     ws = torch.empty(int(lib.eprecon_render_visibility_workspace_bytes(cap)), dtype=torch.uint8, device=dev)
     _lib.check(lib.eprecon_render_visibility_async(
         _lib.ptr(verts), verts.shape[0], _lib.ptr(faces), faces.shape[0], _lib.ptr(cams), v, int(height), int(width),
@@ -80,8 +81,8 @@ def resolve(vis, verts, faces, K, poses, labels=(), backgrounds=(), colors=None,
     `labels` (up to two per-vertex int32[N] device arrays; `backgrounds`, default 0, where nothing is hit), rgb
     uint8[V,H,W,3]: flat shading of `colors` uint8[N,3] (153 grey without) with `background_rgb` where nothing is hit.
     `outputs` names which of depth / face / corner / rgb are produced."""
-    verts, faces = _mesh_tensors(verts, faces)
-    _need_device(vis)
+    verts, faces = mesh_tensors(verts, faces)
+    need_device(vis)
     if vis.dtype not in (torch.uint64, torch.int64) or vis.dim() != 3:
         raise ValueError(f"resolve: expected a 64-bit [V,H,W] visibility buffer, got {vis.dtype} {tuple(vis.shape)}")
     lib = _lib.load()
@@ -97,13 +98,13 @@ def resolve(vis, verts, faces, K, poses, labels=(), backgrounds=(), colors=None,
     n = verts.shape[0]
     labs = []
     for a in labels:
-        _need_device(a)
+        need_device(a)
         a = a.to(torch.int32).contiguous().reshape(-1)
         if a.numel() != n:
             raise ValueError(f"resolve: a label array of {a.numel()} entries for {n} vertices")
         labs.append(a)
     if colors is not None:
-        _need_device(colors)
+        need_device(colors)
         colors = colors.to(torch.uint8).contiguous()
         if tuple(colors.shape) != (n, 3):
             raise ValueError(f"resolve: colours {tuple(colors.shape)} for {n} vertices")
@@ -131,21 +132,21 @@ def resolve(vis, verts, faces, K, poses, labels=(), backgrounds=(), colors=None,
 
 # --------------------------------------------------------------------------------------------------------- conveniences
 
-def _device_mesh(mesh, device=None):
+def device_mesh(mesh, device=None):
     """a tsdf_panoptic2mesh dict, a (verts, faces) pair or a .ply path -> (verts, faces on the device, the dict or {})"""
-    verts, faces = _load_mesh(mesh)
+    verts, faces = load_mesh(mesh)
     dev = torch.device(device if device is not None else (verts.device if isinstance(verts, torch.Tensor) else "cuda"))
-    return _to_dev(verts, torch.float32, dev), _to_dev(faces, torch.int32, dev), (mesh if isinstance(mesh, dict) else {})
+    return to_device(verts, torch.float32, dev), to_device(faces, torch.int32, dev), (mesh if isinstance(mesh, dict) else {})
 
 
 def render_labels(mesh, K, poses, height, width, labels=None, backgrounds=(0, 0), device=None, **raster):
     """-> {depth, face, corner, labels: [...]}.  mesh: one of tsdf_panoptic2mesh's dicts (whichever of vertex_semantic,
     vertex_instance it carries are the default `labels`, in that order), a (verts, faces) pair or a .ply path (geometry
     only: give `labels`, per-vertex int arrays).  **raster: znear, zfar, cull_back, pixel_center."""
-    verts, faces, extra = _device_mesh(mesh, device)
+    verts, faces, extra = device_mesh(mesh, device)
     if labels is None:
         labels = [extra[k] for k in ("vertex_semantic", "vertex_instance") if k in extra]
-    labs = [_to_dev(a, torch.int32, verts.device) for a in labels]
+    labs = [to_device(a, torch.int32, verts.device) for a in labels]
     vis = visibility(verts, faces, K, poses, height, width, **raster)
     return resolve(vis, verts, faces, K, poses, labels=labs, backgrounds=backgrounds,
                    pixel_center=raster.get("pixel_center", 0.5), outputs=("depth", "face", "corner"))
@@ -154,38 +155,30 @@ def render_labels(mesh, K, poses, height, width, labels=None, backgrounds=(0, 0)
 def render_shaded(mesh, K, poses, height, width, colors=None, ambient=DEFAULT_AMBIENT, background_rgb=DEFAULT_BACKGROUND,
                   device=None, **raster):
     """-> uint8[V,H,W,3] on the device.  colors default to the dict's vertex_colors, else the reference's 0.6 grey."""
-    verts, faces, extra = _device_mesh(mesh, device)
+    verts, faces, extra = device_mesh(mesh, device)
     if colors is None:
         colors = extra.get("vertex_colors")
-    col = None if colors is None else _to_dev(colors, torch.uint8, verts.device)
+    col = None if colors is None else to_device(colors, torch.uint8, verts.device)
     vis = visibility(verts, faces, K, poses, height, width, **raster)
     return resolve(vis, verts, faces, K, poses, colors=col, ambient=ambient, background_rgb=background_rgb,
                    pixel_center=raster.get("pixel_center", 0.5), outputs=("rgb",))["rgb"]
 
 
 def scene_mesh(npz_path, device=None):
-    """<scene>.npz in either form SaveScene writes -> (verts f32[N,3] world, faces int32[M,3], semantic, instance int32[N])
+    """<scene>.npz in any layout (scene_io.py) -> (verts f32[N,3] world, faces int32[M,3], semantic, instance int32[N])
     on the device: marching cubes of the TSDF at level 0 with the label volumes sampled at the vertices, as
-    tsdf_panoptic2mesh does.  The sparse form's volumes are built on the device (TSDF default 1, ids default 0)."""
-    verts, faces, _, vsem, vins = scene_mesh_normals(npz_path, device)
+    tsdf_panoptic2mesh does.  Voxel rows become volumes on the device (TSDF default 1, ids default 0)."""
+    verts, faces, _, vsem, vins, _ = scene_mesh_normals(npz_path, device)
     return verts, faces, vsem, vins
 
 
 def scene_mesh_normals(npz_path, device=None):
-    """scene_mesh with marching cubes' normals -> (verts, faces, normals f32[N,3], semantic, instance)"""
+    """scene_mesh with marching cubes' normals and the file's voxel_size -> (verts, faces, normals f32[N,3], semantic,
+    instance, voxel_size)"""
     dev = torch.device(device if device is not None else "cuda")
-    sem, ins, origin, voxel_size = _scene_volumes(npz_path, dev)
-    with np.load(npz_path) as z:
-        rows = "sparse_" if "sparse_tsdf" in z.files else ""
-        values = torch.from_numpy(np.ascontiguousarray(z[rows + "tsdf"], np.float32)).to(dev)
-        if values.dim() == 1:                      # voxel rows: the rest of the volume is the TSDF's default 1
-            c = torch.from_numpy(z[rows + "coords"].astype(np.int64)).to(dev)
-            tsdf = torch.ones(sem.shape, dtype=torch.float32, device=dev)
-            tsdf[c[:, 0], c[:, 1], c[:, 2]] = values
-        else:
-            tsdf = values
+    tsdf, sem, ins, origin, voxel_size = scene_volumes(npz_path, dev)
     verts, faces, normals, vsem, vins = marching_cubes(tsdf, 0.0, labels=(sem, ins))
-    return verts * voxel_size + torch.from_numpy(origin.reshape(1, 3)).to(dev), faces, normals, vsem, vins
+    return verts * voxel_size + torch.from_numpy(origin.reshape(1, 3)).to(dev), faces, normals, vsem, vins, voxel_size
 
 
 def palette_colors(ids):
@@ -250,20 +243,13 @@ def scene_views(data_path, scene, every=10, size=NATIVE_SIZE):
     intrinsic/intrinsic_depth.txt scaled to `size` -> (frame ids, K f64[3,3], poses f64[n,4,4]); frames whose pose is not
     finite are skipped"""
     root = os.path.join(data_path, scene)
-    k = np.loadtxt(os.path.join(root, "intrinsic", "intrinsic_depth.txt"), delimiter=" ")[:3, :3]
-    n = len([f for f in os.listdir(os.path.join(root, "pose")) if f.startswith("pose_") and f.endswith(".txt")])
     ids, poses = [], []
-    for i in range(0, n, max(int(every), 1)):
-        pose = np.loadtxt(os.path.join(root, "pose", f"pose_{i:d}.txt"), delimiter=" ").reshape(4, 4)
-        if np.isfinite(pose).all():
+    for i in pose_frame_ids(root, every):
+        p = pose(root, i)
+        if np.isfinite(p).all():
             ids.append(i)
-            poses.append(pose)
-    return ids, scaled_intrinsics(k, size), np.array(poses, np.float64).reshape(-1, 4, 4)
-
-
-def _read_scenes(path):
-    with open(path, "r", encoding="utf-8") as fh:
-        return [line.strip() for line in fh if line.strip()]
+            poses.append(p)
+    return ids, scaled_intrinsics(intrinsic(root, "depth"), size), np.array(poses, np.float64).reshape(-1, 4, 4)
 
 
 def parse_args(argv=None):
@@ -283,7 +269,7 @@ def main(argv=None):
     modes = ("semantic", "instance", "shaded") if args.mode == "all" else (args.mode,)
     w, h = args.size
     written = []
-    for scene in _read_scenes(args.scenes):
+    for scene in read_scene_list(args.scenes):
         ids, k, poses = scene_views(args.data_path, scene, args.every, (w, h))
         mesh = scene_mesh(os.path.join(args.pred, scene + ".npz"))
         for s in range(0, len(ids), CHUNK):

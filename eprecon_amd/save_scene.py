@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .scene_io import export_ply, read_scene, scatter_volumes, write_scene
 
 # utils.py:243-254 (RGB)
 COLOR_PALETTE = np.array([
@@ -39,8 +40,7 @@ def marching_cubes(volume, level=0.0, labels=(), weight=None):
     the trimmed form — no cell with a corner of weight 0 is meshed (open3d's ExtractTriangleMesh rule; the scene
     evaluation's re-fused volume, eprecon_amd/evaluation.py)"""
     lib = _lib.load()
-    if volume.device.type != "cuda":
-        raise _lib.EpreconError("eprecon_amd operators need device tensors (no CPU fallback)")
+    _lib.need_device(volume)
     vol = volume.to(torch.float32).contiguous()
     dx, dy, dz = vol.shape
     dev = vol.device
@@ -79,7 +79,7 @@ def marching_cubes(volume, level=0.0, labels=(), weight=None):
     return (verts, faces, normals) + tuple(outs)
 
 
-def _mesh(voxel_size, origin, verts, faces, normals):
+def world_mesh(voxel_size, origin, verts, faces, normals):
     origin = torch.as_tensor(origin, dtype=torch.float32, device=verts.device).reshape(1, 3)
     return {"vertices": (verts * float(voxel_size) + origin).cpu().numpy(), "faces": faces.cpu().numpy(),
             "vertex_normals": normals.cpu().numpy()}
@@ -88,77 +88,43 @@ def _mesh(voxel_size, origin, verts, faces, normals):
 def tsdf2mesh(voxel_size, origin, tsdf_vol):
     """utils.py:225-229"""
     verts, faces, normals = marching_cubes(tsdf_vol, 0.0)
-    return _mesh(voxel_size, origin, verts, faces, normals)
+    return world_mesh(voxel_size, origin, verts, faces, normals)
 
 
 def tsdf_panoptic2mesh(voxel_size, origin, tsdf_vol, semantic_vol, instance_vol):
     """utils.py:232-293 -> (mesh, mesh_semantic, mesh_instance): the same geometry with per-vertex colours from the
     palette (semantic id; instance id modulo the palette size); `vertex_semantic` / `vertex_instance` keep the ids"""
     verts, faces, normals, sem, ins = marching_cubes(tsdf_vol, 0.0, labels=(semantic_vol, instance_vol))
-    mesh = _mesh(voxel_size, origin, verts, faces, normals)
+    mesh = world_mesh(voxel_size, origin, verts, faces, normals)
     sem, ins = sem.cpu().numpy(), ins.cpu().numpy()
     mesh_sem = dict(mesh, vertex_colors=COLOR_PALETTE[sem.astype(np.int64) % len(COLOR_PALETTE)], vertex_semantic=sem)
     mesh_ins = dict(mesh, vertex_colors=COLOR_PALETTE[ins.astype(np.int64) % len(COLOR_PALETTE)], vertex_instance=ins)
     return mesh, mesh_sem, mesh_ins
 
 
-def export_ply(mesh, path):
-    """binary little-endian PLY with normals and (when present) RGB vertex colours — what trimesh's mesh.export writes"""
-    v = np.ascontiguousarray(mesh["vertices"], np.float32)
-    n = np.ascontiguousarray(mesh["vertex_normals"], np.float32)
-    f = np.ascontiguousarray(mesh["faces"], np.int32)
-    col = mesh.get("vertex_colors")
-    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
-    if col is not None:
-        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
-    rec = np.zeros(len(v), dtype=fields)
-    rec["x"], rec["y"], rec["z"] = v[:, 0], v[:, 1], v[:, 2]
-    rec["nx"], rec["ny"], rec["nz"] = n[:, 0], n[:, 1], n[:, 2]
-    if col is not None:
-        rec["red"], rec["green"], rec["blue"] = col[:, 0], col[:, 1], col[:, 2]
-    frec = np.zeros(len(f), dtype=[("n", "u1"), ("a", "<i4"), ("b", "<i4"), ("c", "<i4")])
-    frec["n"], frec["a"], frec["b"], frec["c"] = 3, f[:, 0], f[:, 1], f[:, 2]
-    names = {"<f4": "float", "u1": "uchar"}
-    head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"]
-    head += [f"property {names[t]} {k}" for k, t in fields]
-    head += [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
-    with open(path, "wb") as fh:
-        fh.write(("\n".join(head) + "\n").encode("ascii"))
-        fh.write(rec.tobytes())
-        fh.write(frec.tobytes())
-
-
 def load_scene_npz(path):
     """A scene file written by SaveScene -> the reference's dense arrays {origin, voxel_size, tsdf, semantic, instance}
-    (utils.py:360-366), whichever form it was written in.  The sparse form stores the scene as voxel rows
-    (sparse_coords int32[M,3] relative to `origin`, sparse_tsdf f32[M], sparse_semantic / sparse_instance int32[M], dims): the dense volumes
-    (TSDF default 1, ids default 0: models/gru_fusion.py:232-252) are rebuilt here, on the host that wants them."""
-    z = np.load(path)
-    prefix = "sparse_"
-    if "sparse_coords" not in z.files:
-        # files of the earlier sparse layout (round 3: rows under the DENSE key names coords / tsdf / semantic / instance + dims)
-        # are recognised by their 1-D tsdf next to `coords` and `dims` and rebuilt like the current ones, instead of coming
-        # back as 1-D rows under the names a dense reader indexes as volumes
-        if "coords" in z.files and "dims" in z.files and "tsdf" in z.files and z["tsdf"].ndim == 1:
-            prefix = ""
-        else:
+    (utils.py:360-366), whichever layout it was written in (scene_io.read_scene names them).  Rows are rebuilt into the
+    dense volumes (TSDF default 1, ids default 0: models/gru_fusion.py:232-252) here, on the host that wants them; a dense
+    file, and a file of none of the layouts, comes back as the plain key -> array dict."""
+    try:
+        scene = read_scene(path, rest=True)
+    except ValueError:
+        with np.load(path) as z:
             return {k: z[k] for k in z.files}
-    dims, c = tuple(int(d) for d in z["dims"]), z[prefix + "coords"].astype(np.int64)
-    out = {"origin": z["origin"], "voxel_size": z["voxel_size"]}
-    for key, fill, dtype in (("tsdf", 1.0, np.float32), ("semantic", 0, np.int32), ("instance", 0, np.int32)):
-        vol = np.full(dims, fill, dtype)
-        vol[c[:, 0], c[:, 1], c[:, 2]] = z[prefix + key]
-        out[key] = vol
-    return out
+    if scene.layout == "dense":
+        return dict(scene.rest, **scene.arrays)
+    vols = scatter_volumes(scene.dims, scene.coords, scene.arrays)
+    return dict({k: scene.rest[k] for k in ("origin", "voxel_size")}, **{k: v.numpy() for k, v in vols.items()})
 
 
 class SaveScene:
     """utils.py:190-410 (SAVE_SCENE_MESH / SAVE_INCREMENTAL paths; the Open3D incremental viewer is out of scope).
     cfg.SAVE_SCENE_NPZ (beyond the reference's keys): "dense" (default) writes the reference's arrays (utils.py:360-366:
     tsdf / semantic / instance as [X,Y,Z] volumes, what tools/generate_semantic_instance.py and the evaluation scripts
-    index); "sparse" (opt-in) writes the scene as voxel rows under DISTINCT keys (sparse_coords, sparse_tsdf, sparse_semantic,
-    sparse_instance, dims) — a few MB device -> host instead of three dense volumes, and a dense reader fails loudly on the
-    missing keys instead of misreading 1-D rows.  load_scene_npz reads both."""
+    index); "sparse" (opt-in) writes the scene as voxel rows under distinct keys (scene_io's sparse layout) — a few MB
+    device -> host instead of three dense volumes, and a dense reader fails loudly on the missing keys instead of
+    misreading 1-D rows.  load_scene_npz reads both."""
 
     def __init__(self, cfg):
         self.cfg = cfg
@@ -185,17 +151,11 @@ class SaveScene:
         save_path = "{}_fusion_eval_{}".format(self.log_dir, epoch)
         os.makedirs(save_path, exist_ok=True)
         sparse = (outputs.get("scene_sparse") or [None] * (batch_idx + 1))[batch_idx]
+        arrays, head = [tsdf, sem, ins], {"origin": origin.cpu().numpy(), "voxel_size": self._voxel_size()}
         if sparse is not None and str(getattr(self.cfg, "SAVE_SCENE_NPZ", "dense")) == "sparse":
             # the scene as voxel rows: M x (3 + 3) values cross PCIe instead of 3 dense volumes
-            np.savez_compressed(os.path.join(save_path, "{}.npz".format(self.scene_name)),
-                                origin=origin.cpu().numpy(), voxel_size=self._voxel_size(), dims=np.array(sparse["dims"]),
-                                sparse_coords=sparse["coords"].cpu().numpy(), sparse_tsdf=sparse["tsdf"].cpu().numpy(),
-                                sparse_semantic=sparse["semantic"].cpu().numpy(),
-                                sparse_instance=sparse["instance"].cpu().numpy())
-        else:
-            np.savez_compressed(os.path.join(save_path, "{}.npz".format(self.scene_name)),
-                                origin=origin.cpu().numpy(), voxel_size=self._voxel_size(), tsdf=tsdf.cpu().numpy(),
-                                semantic=sem.cpu().numpy(), instance=ins.cpu().numpy())
+            arrays, head["dims"] = [sparse[k] for k in ("tsdf", "semantic", "instance", "coords")], np.array(sparse["dims"])
+        write_scene(os.path.join(save_path, "{}.npz".format(self.scene_name)), *(t.cpu().numpy() for t in arrays), **head)
         export_ply(mesh, os.path.join(save_path, "{}.ply".format(self.scene_name)))
         export_ply(mesh_sem, os.path.join(save_path, "mesh_semantic_{}.ply".format(self.scene_name)))
         export_ply(mesh_ins, os.path.join(save_path, "mesh_instance_{}.ply".format(self.scene_name)))

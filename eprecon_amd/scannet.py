@@ -20,6 +20,7 @@ import pickle
 
 import numpy as np
 
+from .scene_io import depth_metres, intrinsic, pose
 from .transforms import SceneVolumes
 
 MAX_DEPTH = 3.0       # datasets/scannet.py:62
@@ -50,10 +51,7 @@ class ScanNetDataset:
         return len(self.metas)
 
     def read_cam_file(self, filepath, vid):
-        intrinsics = np.loadtxt(os.path.join(filepath, 'intrinsic', 'intrinsic_color.txt'), delimiter=' ')[:3, :3]
-        intrinsics = intrinsics.astype(np.float32)
-        extrinsics = np.loadtxt(os.path.join(filepath, 'pose', 'pose_{:d}.txt'.format(vid)))
-        return intrinsics, extrinsics
+        return intrinsic(filepath, 'color').astype(np.float32), pose(filepath, vid)
 
     def read_img(self, filepath):
         from PIL import Image
@@ -63,17 +61,14 @@ class ScanNetDataset:
 
     def read_depth(self, filepath):
         """16-bit PNG in millimetres: as it is (raw), or as float32 metres with everything beyond 3 m zeroed"""
+        if not self.raw:
+            return depth_metres(filepath, MAX_DEPTH)
         from PIL import Image
         with Image.open(filepath) as im:
             depth_mm = np.asarray(im)
         if depth_mm.dtype != np.uint16:
             depth_mm = depth_mm.astype(np.uint16)         # (PIL's mode "I": the same values as int32)
-        if self.raw:
-            return np.ascontiguousarray(depth_mm)
-        depth_im = depth_mm.astype(np.float32)
-        depth_im /= 1000.
-        depth_im[depth_im > MAX_DEPTH] = 0
-        return depth_im
+        return np.ascontiguousarray(depth_mm)
 
     def read_scene_volumes(self, data_path, scene):
         """{'tsdf_list_full': ...}: the scene's full volumes on the device (with colour and labels in train mode), uploaded

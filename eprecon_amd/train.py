@@ -32,6 +32,7 @@ import torch
 from . import transforms as T
 from .config import ModelCfg
 from .scannet import ScanNetDataset
+from .scene_io import read_scene_list
 
 MAX_READERS = 9       # never sized from the machine
 LW = (1.0, 0.8, 0.64, 1.2)           # config/train.yaml:44
@@ -162,8 +163,7 @@ def main(argv=None):
     dataset = ScanNetDataset(args.data_path, "train", build_transforms(cfg, args.n_views, tuple(args.size), args.epochs, device),
                              args.n_views, len(cfg.MODEL.THRESHOLDS) - 1, source_path=args.source_path, raw=True, device=device)
     if args.scenes:
-        with open(args.scenes, "r", encoding="utf-8") as fh:
-            wanted = {line.strip() for line in fh if line.strip()}
+        wanted = set(read_scene_list(args.scenes))
         dataset.metas = [m for m in dataset.metas if m["scene"] in wanted]
     if len(dataset) == 0:
         raise SystemExit("no fragment to train on")

@@ -409,6 +409,32 @@ def test_cleaned_files_are_read_by_the_mesh_and_the_scorer(CS, tmp_path):
     assert tables[0].tp.sum() == 4 and tables[0].fp.sum() == 0 and tables[0].fn.sum() == 0
 
 
+def test_the_three_layouts_are_one_scene_on_the_device(CS, tmp_path):
+    """tests/scene_io_cases.py's 12 x 10 x 8 scene: every layout gives the same device volumes and the same mesh; the legacy
+    rows are read by the mesh and refused by clean_scene"""
+    import scene_io_cases as SC
+    from eprecon_amd import render, scene_io
+    paths = SC.write_layouts(str(tmp_path))
+    truth = SC.volumes()
+    vols = {k: scene_io.scene_volumes(p, DEV) for k, p in paths.items()}
+    meshes = {k: render.scene_mesh(p) for k, p in paths.items()}
+    for layout in paths:
+        *got, origin, voxel_size = vols[layout]
+        assert np.array_equal(origin, SC.ORIGIN) and voxel_size == SC.VOXEL
+        for vol, want in zip(got, truth):
+            assert vol.device.type == "cuda" and vol.dtype == torch.from_numpy(want).dtype, layout
+            assert np.array_equal(vol.cpu().numpy(), want), layout
+        assert all(torch.equal(x, y) for x, y in zip(meshes[layout], meshes["dense"])), layout
+    verts, faces, vsem, vins = meshes["dense"]
+    assert verts.shape[0] > 50 and faces.shape[0] > 50 and vsem.shape == vins.shape == (verts.shape[0],)
+    with pytest.raises(ValueError, match="neither the dense nor the sparse form"):
+        CS.clean_scene(paths["legacy"], str(tmp_path / "out" / "legacy.npz"))
+    assert not os.path.exists(tmp_path / "out" / "legacy.npz")
+    outs = [CS.clean_scene(paths[k], str(tmp_path / "out" / (k + ".npz")), min_voxels=2)["path"] for k in ("dense", "sparse")]
+    a, b = (scene_io.scene_volumes(p, DEV)[:3] for p in outs)
+    assert all(torch.equal(x, y) for x, y in zip(a, b)) and not torch.equal(a[0], vols["dense"][0])
+
+
 def test_command_line(CS, tmp_path, capsys):
     dense, _ = write_both_forms(str(tmp_path / "pred"))
     os.rename(dense, str(tmp_path / "pred" / "scene0001_00.npz"))

@@ -133,6 +133,6 @@ def test_scene_frames_reads_a_scene_directory(tmp_path):
     assert np.allclose(poses, RR.scene24()[3][[0, 1, 3]], rtol=0, atol=1e-15)
     with image_mod.open(os.path.join(root, "color", "color_3.jpg")) as im:
         assert np.array_equal(frames[2], np.asarray(im.convert("RGB")))
-    assert CZ._frame_ids(data, CC.DISK_SCENE, 2) == [0, 2]
+    assert CZ.pose_frame_ids(root, 2) == [0, 2]
     none = CZ.scene_frames(data, CC.DISK_SCENE, [2])
     assert none[3] == [] and none[0].shape[0] == 0

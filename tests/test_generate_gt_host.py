@@ -139,5 +139,5 @@ def test_depth_png_reader(tmp_path):
     from PIL import Image
     mm = np.array([[0, 500, 2999], [3000, 3001, 65535]], np.uint16)
     Image.fromarray(mm).save(tmp_path / "depth_0.png")
-    d = GG.read_depth(str(tmp_path / "depth_0.png"), 3.0)
+    d = GG.depth_metres(str(tmp_path / "depth_0.png"), 3.0)
     assert d.dtype == np.float32 and np.array_equal(d, np.array([[0, 0.5, 2.999], [3.0, 0, 0]], np.float32))

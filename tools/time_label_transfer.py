@@ -103,7 +103,7 @@ def main(args):
     res = {"dims": list(DIMS), "sites": int((sem_h != 0).sum()), "verts": n, "far_verts": n_far, "reps": args.reps}
 
     # the pieces, device time
-    (_d, dims_p), (_m, map_p) = GSI._c_i32(DIMS), GSI._c_i32(GSI.SCANNET20_MAPPING)
+    (_d, dims_p), (_m, map_p) = GSI.c_i32(DIMS), GSI.c_i32(GSI.SCANNET20_MAPPING)
     masks, n_sites = GSI.brick_masks(sem, GSI.SCANNET20_MAPPING)
     status = torch.empty(2, dtype=torch.int32, device=dev)
     res["bricks"] = events(lambda: _lib.check(lib.eprecon_label_bricks_async(
@@ -114,7 +114,7 @@ def main(args):
     outs = {}
     for path in ("0", "1", "2"):
         os.environ["EPRECON_LT_PATH"] = path
-        query = lambda: GSI._query(masks, sem, ins, ORIGIN, VOXEL_SIZE, verts, GSI.SCANNET20_MAPPING, 2)
+        query = lambda: GSI.query_labels(masks, sem, ins, ORIGIN, VOXEL_SIZE, verts, GSI.SCANNET20_MAPPING, 2)
         res["query"][path] = events(query, args.reps, torch)
         outs[path] = query()
         if path == "0":

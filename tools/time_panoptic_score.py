@@ -103,7 +103,7 @@ def main(args):
     lo, dims = PS._lattice(DIMS, ORIGIN, VOXEL_SIZE, DIMS, GT_ORIGIN, VOXEL_SIZE)
     res.update(pred_segments=P, gt_segments=G, lattice=dims)
     counts, status = PS._table_buffers(P, G, dev)
-    keep = [GSI._c_i32(v) for v in (DIMS, DIMS, lo, dims)]
+    keep = [GSI.c_i32(v) for v in (DIMS, DIMS, lo, dims)]
     o_p, o_g = (ctypes.c_float * 3)(*ORIGIN.tolist()), (ctypes.c_float * 3)(*GT_ORIGIN.tolist())
 
     def voxel_kernel():
