@@ -23,8 +23,8 @@ from . import _lib
 from .global_map import GlobalMap
 from .modules import ConvGRU
 from .tensor import PointTensor
-from .torchsparse_utils import (aligned_camera_coords, convgru_resolution, prepare_convgru_voxelizations,
-                                register_voxelization, register_voxelization_pair)
+from .torchsparse_utils import (aligned_camera_coords, prepare_convgru_voxelizations, register_voxelization,
+                                register_voxelization_pair, voxel_resolution)
 
 
 def fbv_union(cur_coords, cur_feat, glob_coords, glob_feat, dim, interval, rel, mode=0):
@@ -267,7 +267,7 @@ class GRUFusion(nn.Module):
         cfg, gv = self.cfg, self.fusion_nets_voxel[scale]
         chv, cin = self.ch_voxel[scale], self.ch_in[scale]
         chi = cin - chv
-        res = convgru_resolution(gv.convz.pres, gv.convz.vres)
+        res = voxel_resolution(gv.convz.pres, gv.convz.vres)
         tmap = tsdf_gt = occ_gt = None
         if "occ_list" in inputs:
             lvl = cfg.N_LAYER - scale - 1

@@ -39,33 +39,27 @@ def recording():
 # its indice pairs each time (indice_key=None).  Here the hash grid + 27-neighbour table is built
 # once per distinct coords tensor and shared by all layers that see the same tensor.
 # ------------------------------------------------------------------------------------------------
-# The cache is keyed on the tensor OBJECT (identity + data_ptr + torch's version counter).  Writes that the HIP library
-# makes through raw pointers do not bump that counter: a caller that refills the SAME coords tensor in place (e.g. a
-# persistent serving buffer) must call clear_voxel_set_cache() (and torchsparse_utils.clear_voxelization_cache()) at the
-# fragment boundary, or hand over fresh tensors per fragment as every path in this package does.
-_SET_CACHE = []
-_SET_CACHE_MAX = 8
-_SET_CACHE_LOCK = __import__("threading").Lock()   # the pipelined serving mode calls in from a worker thread as well
+# Keyed on (coords tensor, stride): see sparse.IdentityCache for the caveat on tensors refilled in place.
+_SETS = SP.IdentityCache(8)
 
 
 def voxel_set_for(coords, stride=1):
-    key = (coords.data_ptr(), coords.shape[0], coords._version, int(stride), coords.device)
-    with _SET_CACHE_LOCK:
-        for k, ref, vs in _SET_CACHE:
-            if k == key and ref is coords:
-                return vs
-    c = coords if coords.dtype == torch.int32 else coords.to(torch.int32)
-    vs = SP.VoxelSet(c.contiguous(), stride)
-    with _SET_CACHE_LOCK:
-        _SET_CACHE.append((key, coords, vs))
-        if len(_SET_CACHE) > _SET_CACHE_MAX:
-            _SET_CACHE.pop(0)
+    vs = _SETS.get(coords, int(stride))
+    if vs is None:
+        c = coords if coords.dtype == torch.int32 else coords.to(torch.int32)
+        vs = SP.VoxelSet(c.contiguous(), stride)
+        _SETS.put((coords, int(stride), vs))
     return vs
 
 
 def clear_voxel_set_cache():
-    with _SET_CACHE_LOCK:
-        _SET_CACHE.clear()
+    _SETS.clear()
+
+
+def clear_coordinate_caches():
+    """both identity caches of the package: for a caller that refills coordinate tensors in place (sparse.IdentityCache)"""
+    clear_voxel_set_cache()
+    clear_voxelization_cache()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -521,7 +515,8 @@ class Panoptic_Feat_Fusion(nn.Module):
 # torchsparse-style layers: point-voxel U-Net (SPVCNN) and sparse ConvGRU
 # ------------------------------------------------------------------------------------------------
 from .tensor import PointTensor, SparseTensor  # noqa: E402
-from .torchsparse_utils import devoxelize_gate, initial_voxelize, point_to_voxel, voxel_to_point  # noqa: E402
+from .torchsparse_utils import (clear_voxelization_cache, devoxelize_gate, initial_voxelize, point_to_voxel,  # noqa: E402
+                                voxel_to_point)
 
 __all__ = ["SPVCNN", "SConv3d", "ConvGRU"]
 
@@ -778,23 +773,14 @@ class SPVCNN(nn.Module):
             return None
         d, _keep = pack
         pts = z.C if z.C.is_contiguous() else z.C.contiguous()
-        res = float(self.vres) / float(self.pres) if self.pres != 1 else float(self.vres)
-        e = TU._voxelize_points(pts, res, 3)
-        s1 = e.vset
-        if getattr(e, "stride4", None) is None or s1._down is None or s1._down[0]._down is None or s1._k3 is None:
-            return None
-        s2, down12, up21 = s1._down
-        s4, down24, up42 = s2._down
-        if s2._k3 is None or s4._k3 is None or e.idx8 is None:
+        e = TU._voxelize_points(pts, TU.voxel_resolution(self.pres, self.vres), 3)
+        tensors = e.spvcnn_geometry()
+        if tensors is None:
             return None
         lib = _lib.load()
         n = feat.shape[0]
-        d.n, d.n1, d.n2, d.n4 = n, s1.n, s2.n, s4.n
+        d.n, d.n1, d.n2, d.n4 = n, tensors["k1"].shape[1], tensors["k2"].shape[1], tensors["k4"].shape[1]
         d.cin, d.feat, d.ld_feat = feat.shape[1], feat.data_ptr(), feat.stride(0)
-        idx4, (offsets4, order4), idx8_4, w8_4 = e.stride4
-        tensors = {"offsets1": e.lists[0], "order1": e.lists[1], "offsets4": offsets4, "order4": order4, "k1": s1._k3, "k2": s2._k3,
-                   "k4": s4._k3, "down12": down12, "up21": up21, "down24": down24, "up42": up42, "idx8_1": e.idx8,
-                   "weight8_1": e.w8, "idx8_4": idx8_4, "weight8_4": w8_4}
         for name, t in tensors.items():
             setattr(d, name, t.data_ptr())
         out = torch.empty((n, self.cs[4]), dtype=torch.float32, device=feat.device)

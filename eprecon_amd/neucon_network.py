@@ -37,7 +37,7 @@ from .mask3dformer import MultiScaleMaskedTransformerDecoder, panoptic_post
 from .modules import Linear4xTrans, Panoptic_Feat_Fusion, SPVCNN, linear4x_pair
 from .occupancy_initialization import Occupancy_Initialization
 from .tensor import PointTensor
-from .torchsparse_utils import SpvcnnPrefetch, aligned_camera_coords
+from .torchsparse_utils import SpvcnnPrefetch, aligned_camera_coords, voxel_resolution
 
 # the reference's sequence of torch calls (threshold, index_add counts, nonzero, index_select x 4, cat: ~15 launches and two
 # host reads per level) stays for training and the seeded random drop; inference takes eprecon_sparsify_async (3 launches, one
@@ -195,7 +195,7 @@ class NeuConNet(nn.Module):
         on the device count of the rows just compacted; finish -> (up_coords | None, r_coords)"""
         cfg, net = self.cfg, self.sp_convs[level]
         interval = 2 ** (self.n_scales - level)
-        res = float(net.vres) / float(net.pres) if net.pres != 1 else float(net.vres)     # initial_voxelize's resolution
+        res = voxel_resolution(net.pres, net.vres)
 
         def behind(coords, n_dev, extra_out):
             pf = SpvcnnPrefetch(coords, n_dev, children, interval, inputs["vol_origin_partial"], cfg.VOXEL_SIZE,

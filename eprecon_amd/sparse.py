@@ -7,10 +7,49 @@ torchsparse's xyzb order convert at their boundary.
 """
 import ctypes
 import os
+import threading
 
 import torch
 
 from . import _lib
+
+
+class IdentityCache:
+    """What was derived from a tensor's rows, found again for the same tensor: a bounded FIFO keyed on the tensor OBJECT
+    plus (data_ptr, torch's version counter, row count, extra) — modules.voxel_set_for, torchsparse_utils.VOXELIZATIONS.
+    Writes the HIP library makes through raw pointers do not bump the version counter: a caller that refills the SAME tensor
+    in place (a persistent serving buffer) must call modules.clear_coordinate_caches() at the fragment boundary, or hand over
+    fresh tensors per fragment as every path in this package does.  Guarded by a lock: the pipelined serving mode calls in
+    from a worker thread while the main thread runs the next fragment."""
+
+    def __init__(self, max_entries):
+        self._max, self._items, self._lock = int(max_entries), [], threading.Lock()
+
+    @staticmethod
+    def _key(t, extra):
+        return (t.data_ptr(), t._version, t.shape[0], extra)
+
+    def get(self, t, extra=None):
+        key = self._key(t, extra)
+        with self._lock:
+            for k, ref, value in self._items:
+                if ref is t and k == key:
+                    return value
+        return None
+
+    def put(self, *entries):
+        """entries: (tensor, extra, value) each, oldest first; the oldest entries beyond the bound drop out"""
+        with self._lock:
+            self._items.extend((self._key(t, extra), t, value) for t, extra, value in entries)
+            del self._items[:max(0, len(self._items) - self._max)]
+
+    def values(self):
+        with self._lock:
+            return [value for _, _, value in self._items]
+
+    def clear(self):
+        with self._lock:
+            self._items.clear()
 
 
 def _dense3d_level():
@@ -295,10 +334,10 @@ def voxel_hierarchy(vox, levels=3, points=None):
     """The voxel sets of a point cloud at tensor strides 1, 2, 4, ... with ONE host read for all their sizes: the unique
     numbering of `vox` int32[N,4] and of each coarser stride is queued back to back (the coarser calls take the finer
     count from the device, eprecon_unique_coords_dn_async), then the `levels` counts and status words are read together.
-    -> (VoxelSet at stride 1 with its downsample chain attached, inverse int32[N]).
+    -> (VoxelSet at stride 1 with its downsample chain attached, inverse int32[N], tables or None).
     points = scaled f32[N,4] (levels == 3, SPVCNN): everything else a pass needs from the coordinates — CSR point lists and
     trilinear corner tables of strides 1 and 4, the strided maps, the three kernel maps — is queued by ONE library call
-    behind the read (eprecon_spvcnn_geometry_async) -> (VoxelSet, inverse, tables)."""
+    behind the read (eprecon_spvcnn_geometry_async): `tables`, the dict of its 16 tensors."""
     n = vox.shape[0]
     summary = torch.empty(2 * levels, dtype=torch.int32, device=vox.device)
     uniqs, invs, grids = unique_hierarchy_queued(vox, levels, summary=summary)
@@ -312,9 +351,8 @@ def voxel_hierarchy(vox, levels=3, points=None):
     base = VoxelSet(uniqs[0][:sizes[0]], 1, grid=grids[0])
     cur = base
     for lvl in range(1, levels):
-        coarse, _, _ = cur.downsample(pre=(uniqs[lvl][:sizes[lvl]], invs[lvl][:sizes[lvl - 1]], grids[lvl]))
-        cur = coarse
-    return (base, invs[0]) if points is None else (base, invs[0], None)
+        cur = cur.downsample(pre=(uniqs[lvl][:sizes[lvl]], invs[lvl][:sizes[lvl - 1]], grids[lvl]))[0]
+    return base, invs[0], None
 
 
 def _hierarchy_with_geometry(vox, points, grids, uniqs, invs, sizes):
@@ -341,9 +379,11 @@ def _hierarchy_with_geometry(vox, points, grids, uniqs, invs, sizes):
     ws = _lib.workspace(lib.eprecon_spvcnn_geometry_workspace_bytes(n, n1, n4), dev)
     d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
     _lib.check(lib.eprecon_spvcnn_geometry_async(ctypes.byref(d), _lib.current_stream()), "eprecon_spvcnn_geometry_async")
-    s1, s2, s4 = VoxelSet(c1, 1, grid=grids[0]), VoxelSet(c2, 2, grid=grids[1]), VoxelSet(c4, 4, grid=grids[2])
-    s1._k3, s2._k3, s4._k3 = t["k1"], t["k2"], t["k4"]
-    s1._down, s2._down = (s2, t["down12"], t["up21"]), (s4, t["down24"], t["up42"])
+    s1 = VoxelSet(c1, 1, grid=grids[0], kernel_map=t["k1"])
+    s2 = VoxelSet(c2, 2, grid=grids[1], kernel_map=t["k2"])
+    s4 = VoxelSet(c4, 4, grid=grids[2], kernel_map=t["k4"])
+    s1.attach_downsample(s2, t["down12"], t["up21"])
+    s2.attach_downsample(s4, t["down24"], t["up42"])
     return s1, invs[0], t
 
 
@@ -398,18 +438,31 @@ class VoxelSet:
     the kernel maps built on it.  Maps are built once and reused by every layer on the set.
     `dims` (optional): the set lives on the dense grid of dims cells of `stride` voxels starting at 0 (a raster of
     generate_grid, ops/generate_grids.py:3-10) — its 3x3x3 layers then run on the dense-grid kernel when it is full enough.
-    `rank` (optional, with dims): the grid's rank volume int32[cells + 1], already written by the set's producer."""
+    `rank` (optional, with dims): the grid's rank volume int32[cells + 1], already written by the set's producer.
+    `kernel_map` (optional): the [27, N] neighbour table, already written by the set's producer."""
 
-    def __init__(self, coords, stride=1, grid=None, dims=None, rank=None):
+    def __init__(self, coords, stride=1, grid=None, dims=None, rank=None, kernel_map=None):
         assert coords.dtype == torch.int32 and coords.dim() == 2 and coords.shape[1] == 4
         self.coords = coords.contiguous()
         self.stride = int(stride)
         self.dims = None if dims is None else tuple(int(d) for d in dims)
         self._grid = grid
-        self._k3 = None
+        self._k3 = kernel_map
         self._down = None
         self._dense = None
         self._rank = rank        # the rank volume of `dims` when the set's producer wrote it (DenseMap)
+
+    def attach_downsample(self, coarse, down, up):
+        """the k2s2 strided set and its two maps when their producer wrote them already: what downsample() then returns"""
+        self._down = (coarse, down, up)
+
+    def built_kernel_map(self):
+        """the [27, N] table if a layer or the set's producer has built it, else None; launches nothing"""
+        return self._k3
+
+    def built_downsample(self):
+        """(coarse, down, up) if built or attached, else None; launches nothing"""
+        return self._down
 
     def conv_map(self, ksize=3):
         """what a stride-1 k=3 layer on this set takes as its map: a DenseMap for a well-filled dense grid, else the
@@ -432,17 +485,20 @@ class VoxelSet:
             self._grid = HashGrid(self.n, self.coords.device).build(self.coords)
         return self._grid
 
+    def _offset_map(self, centres, ksize):
+        """int32[ksize^3, M]: the rows of this set at the ksize^3 offsets around each of the M rows of `centres`"""
+        nbr = torch.empty((ksize ** 3, centres.shape[0]), dtype=torch.int32, device=self.coords.device)
+        _lib.check(_lib.load().eprecon_kernel_map_async(_lib.ptr(self.grid.mem), self.grid.capacity,
+                                                        _lib.ptr(centres), centres.shape[0], ksize, self.stride,
+                                                        _lib.ptr(nbr), _lib.current_stream()),
+                   "eprecon_kernel_map_async")
+        return nbr
+
     def kernel_map(self, ksize=3):
         """int32[27, N] neighbour table of the stride-1 k=3 convolution on this set"""
         assert ksize == 3
         if self._k3 is None:
-            lib = _lib.load()
-            nbr = torch.empty((27, self.n), dtype=torch.int32, device=self.coords.device)
-            _lib.check(lib.eprecon_kernel_map_async(_lib.ptr(self.grid.mem), self.grid.capacity,
-                                                    _lib.ptr(self.coords), self.n, 3, self.stride,
-                                                    _lib.ptr(nbr), _lib.current_stream()),
-                       "eprecon_kernel_map_async")
-            self._k3 = nbr
+            self._k3 = self._offset_map(self.coords, 3)
         return self._k3
 
     def downsample(self, pre=None):
@@ -454,17 +510,12 @@ class VoxelSet:
             q = 2 * self.stride
             uniq, parent, cgrid = pre if pre is not None else unique_coords(self.coords, quantum=q)
             coarse = VoxelSet(uniq, q, grid=cgrid)
-            m = coarse.n
-            down = torch.empty((8, m), dtype=torch.int32, device=self.coords.device)
-            _lib.check(lib.eprecon_kernel_map_async(_lib.ptr(self.grid.mem), self.grid.capacity,
-                                                    _lib.ptr(coarse.coords), m, 2, self.stride,
-                                                    _lib.ptr(down), _lib.current_stream()),
-                       "eprecon_kernel_map_async")
+            down = self._offset_map(coarse.coords, 2)
             up = torch.empty((8, self.n), dtype=torch.int32, device=self.coords.device)
             _lib.check(lib.eprecon_transpose_map_async(_lib.ptr(self.coords), self.n, _lib.ptr(parent),
                                                        self.stride, _lib.ptr(up), _lib.current_stream()),
                        "eprecon_transpose_map_async")
-            self._down = (coarse, down, up)
+            self.attach_downsample(coarse, down, up)
         return self._down
 
 

@@ -72,7 +72,25 @@ class _VoxEntry:
     (scaled points, voxel set + hash grid + kernel map, point -> voxel lists, trilinear corners / weights).
     The six SConv3d of the two ConvGRUs of a scale voxelise the same points: convz and convq of both GRUs
     share one entry, both convr the entry built on the already-scaled coordinates."""
-    __slots__ = ("key", "pts", "scaled", "vox", "vset", "inverse", "lists", "idx8", "w8", "_order", "_stale", "stride4")
+    __slots__ = ("pts", "res", "scaled", "vox", "vset", "inverse", "tables", "lists", "idx8", "w8", "_order", "_stale")
+
+    def __init__(self, pts, res, scaled, vox, vset, inverse, tables=None, lists=None, corners=(None, None), order=None):
+        """(pts, res): the cache key.  (vset, inverse, tables): what sparse.voxel_hierarchy returns — with tables, the point
+        lists and corner tables are read from that dict.  Without: lists = (offsets, order), corners = (idx8, w8) and order
+        = sphash_order() where their producer wrote them (the ConvGRU stage call); else the lists are queued here, the corner
+        tables by their first reader (_entry_corner_tables, _corner_tables)"""
+        self.pts, self.res = pts, float(res)
+        self.scaled, self.vox, self.vset, self.inverse, self.tables = scaled, vox, vset, inverse, tables
+        if tables is not None:
+            lists, corners = (tables["offsets1"], tables["order1"]), (tables["idx8_1"], tables["weight8_1"])
+        self.lists = lists if lists is not None else _segment_lists(inverse, vset.n)
+        self.idx8, self.w8 = corners
+        self._order, self._stale = order, {}
+
+    def spvcnn_geometry(self):
+        """the 15 geometry tensors of eprecon_spvcnn_forward_desc by field name — the tables without the stride-4 point ids,
+        which only the Python-issued pass reads —, or None when the entry did not come out of the hierarchy call"""
+        return None if self.tables is None else {name: t for name, t in self.tables.items() if name != "idx4"}
 
     def sphash_order(self):
         """(perm, rank): perm[k] = id of the voxel with the k-th smallest torchsparse hash, rank = its inverse —
@@ -107,69 +125,37 @@ class _VoxEntry:
         return hit[0], hit[1]
 
 
-# Keyed on the point tensor OBJECT (identity + data_ptr + torch's version counter): a caller that refills the same tensor in
-# place through raw pointers (which does not bump the counter) must call clear_voxelization_cache() at the fragment boundary;
-# every path in this package hands over a fresh tensor per fragment.  Guarded by a lock: the pipelined serving mode calls in
-# from a worker thread while the main thread runs the next fragment.
-_VOX_CACHE = []
-_VOX_CACHE_MAX = 6
-_VOX_CACHE_LOCK = __import__("threading").Lock()
+# the voxelisations of the current fragment, keyed on (point tensor, resolution): see sparse.IdentityCache for the caveat on
+# tensors refilled in place
+VOXELIZATIONS = SP.IdentityCache(6)
 
 
 def clear_voxelization_cache():
-    with _VOX_CACHE_LOCK:
-        _VOX_CACHE.clear()
+    VOXELIZATIONS.clear()
 
 
-def _cached_entry(key, pts):
-    with _VOX_CACHE_LOCK:
-        for e in _VOX_CACHE:
-            if e.key == key and e.pts is pts:
-                return e
-    return None
-
-
-def _publish_entry(e):
-    e.lists = _segment_lists(e.inverse, e.vset.n)
-    e.idx8 = e.w8 = e._order = e.stride4 = None
-    e._stale = {}
-    with _VOX_CACHE_LOCK:
-        _VOX_CACHE.append(e)
-        if len(_VOX_CACHE) > _VOX_CACHE_MAX:
-            _VOX_CACHE.pop(0)
-    return e
+def _publish(*entries):
+    VOXELIZATIONS.put(*((e.pts, e.res, e) for e in entries))
+    return entries[0]
 
 
 def _voxelize_points(pts, res, levels=1):
     """levels > 1 (SPVCNN): the strided voxel sets of the U-Net's down stages are numbered in the same pass and ALL sizes are
     read back at once (sparse.voxel_hierarchy) — one host read per SPVCNN pass instead of three"""
-    key = (pts.data_ptr(), pts._version, pts.shape[0], float(res))
-    e = _cached_entry(key, pts)
+    e = VOXELIZATIONS.get(pts, float(res))
     if e is not None:
         return e
     lib = _lib.load()
     n = pts.shape[0]
-    e = _VoxEntry()
-    e.key, e.pts = key, pts
-    e.scaled = torch.empty_like(pts)
-    e.vox = torch.empty((n, 4), dtype=torch.int32, device=pts.device)
-    _lib.check(lib.eprecon_point_quantize_async(_lib.ptr(pts), n, float(res), _lib.ptr(e.scaled), _lib.ptr(e.vox),
+    scaled = torch.empty_like(pts)
+    vox = torch.empty((n, 4), dtype=torch.int32, device=pts.device)
+    _lib.check(lib.eprecon_point_quantize_async(_lib.ptr(pts), n, float(res), _lib.ptr(scaled), _lib.ptr(vox),
                                                 _lib.current_stream()), "eprecon_point_quantize_async")
     if levels > 1 and pts.is_cuda:
-        e.vset, e.inverse, tables = SP.voxel_hierarchy(e.vox, levels, points=e.scaled)
-        if tables is not None:
-            # the pass's whole geometry came out of one library call: publish the entry complete
-            e.lists = (tables["offsets1"], tables["order1"])
-            e.idx8, e.w8, e._order, e._stale = tables["idx8_1"], tables["weight8_1"], None, {}
-            e.stride4 = (tables["idx4"], (tables["offsets4"], tables["order4"]), tables["idx8_4"], tables["weight8_4"])
-            with _VOX_CACHE_LOCK:
-                _VOX_CACHE.append(e)
-                del _VOX_CACHE[:max(0, len(_VOX_CACHE) - _VOX_CACHE_MAX)]
-            return e
-    else:
-        uniq, e.inverse, grid = SP.unique_coords(e.vox, 1)
-        e.vset = SP.VoxelSet(uniq, 1, grid=grid)
-    return _publish_entry(e)
+        # (with tables, the pass's whole geometry came out of one library call: the entry is published complete)
+        return _publish(_VoxEntry(pts, res, scaled, vox, *SP.voxel_hierarchy(vox, levels, points=scaled)))
+    uniq, inverse, grid = SP.unique_coords(vox, 1)
+    return _publish(_VoxEntry(pts, res, scaled, vox, SP.VoxelSet(uniq, 1, grid=grid), inverse))
 
 
 class SpvcnnPrefetch:
@@ -224,17 +210,9 @@ class SpvcnnPrefetch:
         up = self.up[:n_pts] if self.up is not None else None
         if n_pts == 0 or sizes[0] == 0:
             return up, r
-        e = _VoxEntry()
-        e.key, e.pts = (r.data_ptr(), r._version, r.shape[0], self.res), r
-        e.scaled, e.vox = self.scaled[:n_pts], self.vox[:n_pts]
+        scaled, vox = self.scaled[:n_pts], self.vox[:n_pts]
         invs = [self.invs[0][:n_pts], self.invs[1], self.invs[2]]
-        e.vset, e.inverse, tables = SP._hierarchy_with_geometry(e.vox, e.scaled, self.grids, self.uniqs, invs, sizes)
-        e.lists = (tables["offsets1"], tables["order1"])
-        e.idx8, e.w8, e._order, e._stale = tables["idx8_1"], tables["weight8_1"], None, {}
-        e.stride4 = (tables["idx4"], (tables["offsets4"], tables["order4"]), tables["idx8_4"], tables["weight8_4"])
-        with _VOX_CACHE_LOCK:
-            _VOX_CACHE.append(e)
-            del _VOX_CACHE[:max(0, len(_VOX_CACHE) - _VOX_CACHE_MAX)]
+        _publish(_VoxEntry(r, self.res, scaled, vox, *SP._hierarchy_with_geometry(vox, scaled, self.grids, self.uniqs, invs, sizes)))
         return up, r
 
 
@@ -242,11 +220,7 @@ def register_voxelization(pts, res, scaled, vox, inverse, uniq, grid):
     """An entry whose quantisation and voxel numbering were computed elsewhere with device-side counts (GRU-fusion stage,
     eprecon_gru_stage_begin_async) and already sliced to their sizes: published under the points tensor `pts` so that the
     SConv3d that voxelise these points find it (initial_voxelize)"""
-    e = _VoxEntry()
-    e.key, e.pts = (pts.data_ptr(), pts._version, pts.shape[0], float(res)), pts
-    e.scaled, e.vox, e.inverse = scaled, vox, inverse
-    e.vset = SP.VoxelSet(uniq, 1, grid=grid)
-    return _publish_entry(e)
+    return _publish(_VoxEntry(pts, res, scaled, vox, SP.VoxelSet(uniq, 1, grid=grid), inverse))
 
 
 def register_voxelization_pair(pts, res, first, second):
@@ -272,57 +246,50 @@ def register_voxelization_pair(pts, res, first, second):
     idx1, w1, idx2 = i32(n, 8), torch.empty((n, 8), dtype=torch.float32, device=dev), i32(n, 8)
     d.offsets1, d.order1, d.offsets2, d.order2 = off1.data_ptr(), ord1.data_ptr(), off2.data_ptr(), ord2.data_ptr()
     d.nbr1, d.nbr2, d.idx8_1, d.weight8_1, d.idx8_2 = nbr1.data_ptr(), nbr2.data_ptr(), idx1.data_ptr(), w1.data_ptr(), idx2.data_ptr()
-    w2 = order = None
+    w2 = order1 = order2 = None
     if LITERAL_CONVR:
-        order = i32(2, m1), i32(2, m2)
-        d.perm1, d.rank1, d.perm2, d.rank2 = order[0][0].data_ptr(), order[0][1].data_ptr(), order[1][0].data_ptr(), order[1][1].data_ptr()
+        order1, order2 = tuple(i32(2, m1)), tuple(i32(2, m2))      # (perm, rank) of each set: sphash_order()
+        d.perm1, d.rank1, d.perm2, d.rank2 = (t.data_ptr() for t in order1 + order2)
     else:
         w2 = torch.empty((n, 8), dtype=torch.float32, device=dev)
         d.weight8_2 = w2.data_ptr()
     ws = _lib.workspace(lib.eprecon_gru_stage_finish_workspace_bytes(n, m1, m2), dev)
     d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
     _lib.check(lib.eprecon_gru_stage_finish_async(ctypes.byref(d), _lib.current_stream()), "eprecon_gru_stage_finish_async")
-    entries = []
-    for src, scaled, vox, inv, uq, grid, lists, nbr in ((pts, sc1, vox1, inv1, uq1, g1, (off1, ord1), nbr1),
-                                                         (sc1, sc2, vox2, inv2, uq2, g2, (off2, ord2), nbr2)):
-        e = _VoxEntry()
-        e.key, e.pts = (src.data_ptr(), src._version, src.shape[0], float(res)), src
-        e.scaled, e.vox, e.inverse, e.lists = scaled, vox, inv, lists
-        e.vset = SP.VoxelSet(uq, 1, grid=grid)
-        e.vset._k3 = nbr
-        e.idx8 = e.w8 = e._order = None
-        e._stale = {}
-        entries.append(e)
-    e1, e2 = entries
-    e1.idx8, e1.w8 = idx1, w1
-    if LITERAL_CONVR:
-        e1._order, e2._order = (order[0][0], order[0][1]), (order[1][0], order[1][1])
+    set1, set2 = SP.VoxelSet(uq1, 1, grid=g1, kernel_map=nbr1), SP.VoxelSet(uq2, 1, grid=g2, kernel_map=nbr2)
+    e1 = _VoxEntry(pts, res, sc1, vox1, set1, inv1, lists=(off1, ord1), corners=(idx1, w1), order=order1)
+    e2 = _VoxEntry(sc1, res, sc2, vox2, set2, inv2, lists=(off2, ord2), corners=(None, None) if LITERAL_CONVR else (idx2, w2),
+                   order=order2)
+    if LITERAL_CONVR:     # idx2 = the first entry's corner indices remapped into the second set: what stale_from(e1) answers
         e2._stale[id(e1)] = (idx2, w1, e1)
-    else:
-        e2.idx8, e2.w8 = idx2, w2
-    with _VOX_CACHE_LOCK:
-        _VOX_CACHE.extend(entries)
-        del _VOX_CACHE[:max(0, len(_VOX_CACHE) - _VOX_CACHE_MAX)]
+    _publish(e1, e2)
     return e1, e2
+
+
+def _trilinear_tables(vset, s, pts):
+    """-> (int32[N,8] corner indices, f32[N,8] renormalised trilinear weights) of `pts` (voxel units) against `vset` at
+    tensor stride s, by hash probes"""
+    lib = _lib.load()
+    n = pts.shape[0]
+    idx8 = torch.empty((n, 8), dtype=torch.int32, device=pts.device)
+    w8 = torch.empty((n, 8), dtype=torch.float32, device=pts.device)
+    grid = vset.grid
+    _lib.check(lib.eprecon_trilinear_map_async(_lib.ptr(grid.mem), grid.capacity, _lib.ptr(pts), n, s,
+                                               _lib.ptr(idx8), _lib.ptr(w8), _lib.current_stream()),
+               "eprecon_trilinear_map_async")
+    return idx8, w8
 
 
 def _entry_corner_tables(e):
     """corner indices / weights of an entry's own points against its own voxel set (what the first voxel_to_point of
     an SConv3d on these points computes)"""
     if e.idx8 is None:
-        lib = _lib.load()
-        n = e.scaled.shape[0]
-        idx8 = torch.empty((n, 8), dtype=torch.int32, device=e.scaled.device)
-        w8 = torch.empty((n, 8), dtype=torch.float32, device=e.scaled.device)
-        grid = e.vset.grid
-        _lib.check(lib.eprecon_trilinear_map_async(_lib.ptr(grid.mem), grid.capacity, _lib.ptr(e.scaled), n, 1,
-                                                   _lib.ptr(idx8), _lib.ptr(w8), _lib.current_stream()),
-                   "eprecon_trilinear_map_async")
-        e.idx8, e.w8 = idx8, w8
+        e.idx8, e.w8 = _trilinear_tables(e.vset, 1, e.scaled)
     return e.idx8, e.w8
 
 
-def convgru_resolution(init_res, after_res):
+def voxel_resolution(init_res, after_res):
+    """what initial_voxelize divides a layer's coordinates by (ops/torchsparse_utils.py:17): THE rule, for every caller"""
     return float(after_res) / float(init_res) if init_res != 1 else float(after_res)
 
 
@@ -331,7 +298,7 @@ def prepare_convgru_voxelizations(coords, init_res, after_res):
     voxelisation of `coords` (convz / convq) and of the once-scaled coordinates (convr), their kernel maps and corner
     tables (stale ones in LITERAL_CONVR mode).  Afterwards the two cells only READ these entries and can run on two
     streams.  (Entries registered by the GRU-fusion stage call are found in the cache: no quantise / unique / host read.)"""
-    res = convgru_resolution(init_res, after_res)
+    res = voxel_resolution(init_res, after_res)
     pts = coords if coords.is_contiguous() else coords.contiguous()
     e1 = _voxelize_points(pts, res)
     e1.vset.kernel_map(3)
@@ -355,7 +322,7 @@ def initial_voxelize(z, init_res, after_res, levels=1):
     devoxelising with the FIRST call's corner indices and weights, now pointing into the second voxel set
     in torchsparse's ascending-hash voxel order (LITERAL_CONVR)."""
     pts = z.C if z.C.is_contiguous() else z.C.contiguous()
-    res = float(after_res) / float(init_res) if init_res != 1 else float(after_res)
+    res = voxel_resolution(init_res, after_res)
     prev = getattr(z, "_vox_entry", None)
     e = _voxelize_points(pts, res, levels)
     feat = _segment_mean(z.F, e.lists, e.vset.n, idx=e.inverse)
@@ -371,11 +338,11 @@ def initial_voxelize(z, init_res, after_res, levels=1):
     z.additional_features["lists"].clear()
     z.additional_features["idx_query"][1] = e.inverse
     z.additional_features["lists"][1] = e.lists
-    s4 = getattr(e, "stride4", None)
-    if s4 is not None and not (prev is not None and LITERAL_CONVR):
+    t = e.tables
+    if t is not None and not (prev is not None and LITERAL_CONVR):
         # (SPVCNN: the stride-4 transfers of the pass were tabulated with the rest of its geometry)
-        z.additional_features["idx_query"][4], z.additional_features["lists"][4] = s4[0], s4[1]
-        z.idx_query[4], z.weights[4] = s4[2], s4[3]
+        z.additional_features["idx_query"][4], z.additional_features["lists"][4] = t["idx4"], (t["offsets4"], t["order4"])
+        z.idx_query[4], z.weights[4] = t["idx8_4"], t["weight8_4"]
     z._vox_entry = e
     return SparseTensor(feat, e.vset)
 
@@ -396,14 +363,7 @@ def _corner_tables(vset, s, z):
     """8-corner indices / renormalised trilinear weights of the points of z against `vset` at tensor stride s,
     cached on the PointTensor like the reference's z.idx_query / z.weights (ops/torchsparse_utils.py:70-96)"""
     if s not in z.idx_query:
-        lib = _lib.load()
-        n = z.C.shape[0]
-        idx8 = torch.empty((n, 8), dtype=torch.int32, device=z.C.device)
-        w8 = torch.empty((n, 8), dtype=torch.float32, device=z.C.device)
-        grid = vset.grid
-        _lib.check(lib.eprecon_trilinear_map_async(_lib.ptr(grid.mem), grid.capacity, _lib.ptr(z.C), n, s,
-                                                   _lib.ptr(idx8), _lib.ptr(w8), _lib.current_stream()),
-                   "eprecon_trilinear_map_async")
+        idx8, w8 = _trilinear_tables(vset, s, z.C)
         z.idx_query[s], z.weights[s] = idx8, w8
         e = getattr(z, "_vox_entry", None)
         if s == 1 and e is not None and e.vset is vset and e.idx8 is None:

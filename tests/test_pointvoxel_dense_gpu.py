@@ -73,7 +73,7 @@ def test_numbering_parents_and_strided_maps_on_negative_coordinates():
         ru, rinv = DR.number_first(DR.quantise_coords(c, q))
         assert np.array_equal(host(u), ru) and np.array_equal(host(inv), rinv), f"quantum {q}"
     lv = hierarchy(c)
-    base, inv = SP.voxel_hierarchy(dev(c), 3)
+    base, inv, _ = SP.voxel_hierarchy(dev(c), 3)
     assert np.array_equal(host(base.coords), lv[0][0]) and np.array_equal(host(inv), np.arange(len(c)))
     cur = base
     for lvl in range(1, 4):      # levels 1, 2 from the hierarchy call, level 3 (stride 8) by VoxelSet.downsample()

@@ -23,7 +23,8 @@ def main():
     step.run()                                  # the last fragment of the scene: the largest map state
     torch.cuda.synchronize()
     # the kernel maps of the fragment's voxelisations are in the cache the SConv3d layers read (the finest level's last)
-    maps = [e.vset._k3 for e in TU._VOX_CACHE if e.vset._k3 is not None and e.vset._k3.shape[1] > 200000]
+    maps = [e.vset.built_kernel_map() for e in TU.VOXELIZATIONS.values()]
+    maps = [m for m in maps if m is not None and m.shape[1] > 200000]
     cands = [(float((m >= 0).float().mean()), m) for m in maps]
     cands = [c for c in cands if c[0] > 0.2]    # (the second ConvGRU voxelisation has no adjacent voxels: 1 / 27 live)
     live_frac, nbr = max(cands, key=lambda c: c[1].shape[1])

@@ -89,7 +89,8 @@ def main():
             for _ in range(2 * step.n_fragments):
                 step.run()
             torch.cuda.synchronize()
-            maps = [e.vset._k3 for e in TU._VOX_CACHE if e.vset._k3 is not None and e.vset._k3.shape[1] > 200000]
+            maps = [e.vset.built_kernel_map() for e in TU.VOXELIZATIONS.values()]
+            maps = [m for m in maps if m is not None and m.shape[1] > 200000]
             cands = [m for m in maps if float((m >= 0).float().mean()) > 0.2]
             nbr = max(cands, key=lambda m: m.shape[1])
             n = nbr.shape[1]

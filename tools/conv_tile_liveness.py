@@ -21,7 +21,7 @@ _orig_pair = TU.register_voxelization_pair
 
 
 def recording_kernel_map(self, ksize=3):
-    fresh = self._k3 is None
+    fresh = self.built_kernel_map() is None
     nbr = _orig(self, ksize)
     if fresh:
         MAPS.append((self.stride, nbr))
@@ -32,14 +32,15 @@ def recording_kernel_map(self, ksize=3):
 # where the call hands them over)
 def recording_hierarchy(*a, **k):
     s1, inv, t = _orig_hier(*a, **k)
-    s2 = s1._down[0]
-    MAPS.extend([(1, s1._k3), (2, s2._k3), (4, s2._down[0]._k3)])
+    s2 = s1.built_downsample()[0]
+    s4 = s2.built_downsample()[0]
+    MAPS.extend([(1, s1.built_kernel_map()), (2, s2.built_kernel_map()), (4, s4.built_kernel_map())])
     return s1, inv, t
 
 
 def recording_pair(*a, **k):
     e1, e2 = _orig_pair(*a, **k)
-    MAPS.extend([(1, e1.vset._k3), (1, e2.vset._k3)])
+    MAPS.extend([(1, e1.vset.built_kernel_map()), (1, e2.vset.built_kernel_map())])
     return e1, e2
 
 
