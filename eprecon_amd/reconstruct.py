@@ -1,7 +1,7 @@
 """Reconstruct scenes from disk — the reference's test loop (main.py:104-121, :376-405, :429-436) as a tool:
 
     python -m eprecon_amd.reconstruct --data_path DIR [--source_path DIR] [--mode test|val] [--ckpt FILE] --out DIR \\
-           [--scenes FILE] [--n_views 9] [--size 640 480] [--host-views] [--color] [--clean N [--clean_segments N]]
+           [--scenes FILE] [--n_views 9] [--size 640 480] [--host-views] [--color] [--clean N [--clean_segments N]] [--objects]
 
 reads <data_path>/all_tsdf_<n_views>_1/fragments_<mode>.pkl (eprecon_amd.generate_gt writes it) and the frames it names
 (scannet.ScanNetDataset), and walks the fragments in file order, one per step: PrepareViews -> RandomTransformSpace (no
@@ -25,6 +25,9 @@ is written (eprecon_amd.colorize) and puts mesh_color_<scene>.ply beside the oth
 --clean N (off by default) cleans every saved scene once it is written (eprecon_amd.clean_scene: connected pieces of the
 surface below N voxels are removed; with --clean_segments N, pieces of a segment below N voxels lose their ids) and puts
 the cleaned <scene>.npz and its three meshes into clean/ beside the saved scene; no other file changes.
+
+--objects (off by default) writes <scene>_objects.json beside every saved scene once it is written: one record per segment
+with its voxel count, centroid, axis-aligned box and upright oriented box (eprecon_amd.scene_objects); no other file changes.
 """
 import argparse
 import os
@@ -72,6 +75,7 @@ def parse_args(argv=None):
                                                             "its connected pieces of fewer than N voxels")
     ap.add_argument("--clean_segments", default=0, type=int, metavar="N", help="with --clean: pieces of a segment of fewer "
                                                                                 "than N voxels lose their ids")
+    ap.add_argument("--objects", action="store_true", help="also write <scene>_objects.json: count, centroid and boxes per segment")
     return ap.parse_args(argv)
 
 
@@ -128,6 +132,18 @@ def clean_saved_scenes(outputs, saver, epoch, min_voxels, min_segment_voxels):
             report = clean_scene(npz, os.path.join(save_path, "clean", scene + ".npz"), mesh=True, min_voxels=min_voxels,
                                  min_segment_voxels=min_segment_voxels)
             print(f"[reconstruct] {format_report(name, report)}")
+
+
+def describe_saved_scenes(outputs, saver, epoch):
+    """--objects: the inventory of the scenes this step saved, as <scene>_objects.json beside them"""
+    from .scene_objects import describe_scene, format_objects
+    save_path = "{}_fusion_eval_{}".format(saver.log_dir, epoch)
+    for name in outputs.get("scene_name", []):
+        scene = name.replace("/", "-")
+        npz = os.path.join(save_path, scene + ".npz")
+        if os.path.exists(npz):
+            path = os.path.join(save_path, scene + "_objects.json")
+            print(f"[reconstruct] {format_objects(name, describe_scene(npz, path), path)}")
 
 
 def main(argv=None):
@@ -202,6 +218,8 @@ def main(argv=None):
                 color_saved_scenes(outputs, saver, epoch, dataset.source_path, key_frames, float(cfg.MODEL.VOXEL_SIZE))
             if args.clean is not None:
                 clean_saved_scenes(outputs, saver, epoch, args.clean, args.clean_segments)
+            if args.objects:
+                describe_saved_scenes(outputs, saver, epoch)
             count += 1
         torch.cuda.synchronize(device)
         report(scene, count, time.perf_counter() - t_scene, read_s, prepare_s)

@@ -230,7 +230,11 @@ def load_mesh(mesh_or_path):
 
 
 def export_ply(mesh, path):
-    """binary little-endian PLY with normals and (when present) RGB vertex colours — what trimesh's mesh.export writes"""
+    """binary little-endian PLY with normals and (when present) RGB vertex colours — what trimesh's mesh.export writes.
+    A mesh with "edges" int[E,2] is a wireframe instead: vertices without normals, no faces, an `edge` element of
+    vertex1 / vertex2 (the boxes of scene_objects)."""
+    if mesh.get("edges") is not None:
+        return _export_edges_ply(mesh, path)
     v = np.ascontiguousarray(mesh["vertices"], np.float32)
     n = np.ascontiguousarray(mesh["vertex_normals"], np.float32)
     f = np.ascontiguousarray(mesh["faces"], np.int32)
@@ -253,6 +257,28 @@ def export_ply(mesh, path):
         fh.write(("\n".join(head) + "\n").encode("ascii"))
         fh.write(rec.tobytes())
         fh.write(frec.tobytes())
+
+
+def _export_edges_ply(mesh, path):
+    v = np.ascontiguousarray(mesh["vertices"], np.float32).reshape(-1, 3)
+    e = np.ascontiguousarray(mesh["edges"], np.int32).reshape(-1, 2)
+    col = mesh.get("vertex_colors")
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("red", "u1"), ("green", "u1"), ("blue", "u1")] if col is not None else [])
+    rec = np.zeros(len(v), dtype=fields)
+    rec["x"], rec["y"], rec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if col is not None:
+        col = np.asarray(col).reshape(-1, 3)
+        rec["red"], rec["green"], rec["blue"] = col[:, 0], col[:, 1], col[:, 2]
+    erec = np.zeros(len(e), dtype=[("vertex1", "<i4"), ("vertex2", "<i4")])
+    erec["vertex1"], erec["vertex2"] = e[:, 0], e[:, 1]
+    names = {"<f4": "float", "u1": "uchar"}
+    head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"]
+    head += [f"property {names[t]} {k}" for k, t in fields]
+    head += [f"element edge {len(e)}", "property int vertex1", "property int vertex2", "end_header"]
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(head) + "\n").encode("ascii"))
+        fh.write(rec.tobytes())
+        fh.write(erec.tobytes())
 
 
 # ----------------------------------------------------------------------------------- a ScanNet-layout scene directory

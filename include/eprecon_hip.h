@@ -1097,6 +1097,35 @@ int eprecon_voxel_pair_count_async(const int32_t *pred_rank, const int32_t *gt_r
                                    int64_t *counts, int32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Object inventory: per-segment statistics of voxel rows  (csrc/segment_stats.hip, eprecon_amd/scene_objects.py; the
+ * reference has no counterpart: the rule is DESIGN.md 5b's)
+ *
+ * coords int32[m,3] (x, y, z) and rank int32[m] on the device; m < 2^24 and n_segments <= 2^24, else
+ * EPRECON_ERR_UNSUPPORTED before any launch.  Row i takes part when 0 <= rank[i] < n_segments and every |coordinate| is at
+ * most 2^19 - 2 (the hash grid's range).  The rank is looked at first: -1 ("nothing here") and n_segments (void) are skipped
+ * silently; any other rank outside the range is skipped and sets status |= 1; a row with a rank in range and a coordinate
+ * out of range is skipped and sets status |= 2.  status int32[1] and the whole output are initialised by the call (one
+ * launch), so the caller passes uninitialised buffers; a segment without rows keeps the initial values.  m == 0 or
+ * n_segments == 0: nothing but that initialisation is launched and no row is looked at.
+ *
+ * eprecon_segment_moments_async: table int64[n_segments,16]: column 0 the count; 1-3 the sums of x, y, z; 4-9 the sums of
+ *   xx, xy, xz, yy, yz, zz (below 2^62 under the limits above); 10-12 min x, y, z (initially INT32_MAX); 13-15 max x, y, z
+ *   (initially INT32_MIN).
+ * eprecon_segment_extents_async: with (c, s) = dirs[rank] (double[n_segments,2], finite), u = fl(fl(x c) + fl(y s)) and
+ *   v = fl(fl(y c) - fl(x s)) in fp64, ext double[n_segments,4] = (min u, max u, min v, max v), initially (+inf, -inf,
+ *   +inf, -inf).  A zero counts as +0, so the bits are the same on every run.
+ *
+ * Integer sums and min / max only: the output depends neither on the order nor on the path.  With up to
+ * eprecon_segment_stats_lds_segments() segments the updates are combined per workgroup in LDS first and sent to memory once
+ * per workgroup (EPRECON_SS_LDS=0: never); above it every update goes straight to memory.
+ * ------------------------------------------------------------------------------------------ */
+int32_t eprecon_segment_stats_lds_segments(void);
+int eprecon_segment_moments_async(const int32_t *coords, const int32_t *rank, int64_t m, int32_t n_segments, int64_t *table,
+                                  int32_t *status, void *stream);
+int eprecon_segment_extents_async(const int32_t *coords, const int32_t *rank, int64_t m, int32_t n_segments, const double *dirs,
+                                  double *ext, int32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Nearest finest-level voxel  (K18)
  *
  * Replaces  torch.cdist + argmin(dim=1)                 models/mask3dformer.py:361-367
