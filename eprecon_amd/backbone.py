@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, weight_cache
 
 BACKBONE_HIP = os.environ.get("EPRECON_BACKBONE_HIP", "1") == "1"
 
@@ -208,14 +208,9 @@ def bn_views_apply(x, aff, v, relu, residual=None):
 
 
 def _dw_taps(conv):
-    """[C, 1, k, k] -> tap-major [k*k, C], cached per weight version"""
-    w = conv.weight
-    tag = (w._version, w.data_ptr())
-    hit = getattr(conv, "_eprecon_packed", None)
-    if hit is None or hit[0] != tag:
-        hit = (tag, w.detach().reshape(w.shape[0], -1).t().contiguous())
-        conv._eprecon_packed = hit
-    return hit[1]
+    """[C, 1, k, k] -> tap-major [k*k, C] (cached: weight_cache)"""
+    w = conv._parameters["weight"]
+    return weight_cache.derived(conv, "backbone.dw_taps", (w,), lambda: w.detach().reshape(w.shape[0], -1).t().contiguous())
 
 
 def dwconv_nhwc(conv, x, v, pending=None):

@@ -17,7 +17,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, weight_cache
 from . import sparse as SP
 
 
@@ -63,16 +63,14 @@ def maps_of(rows, maps, height, width):
 
 
 def packed_weight(conv):
-    """nn.Conv2d weight [C_out, C_in, k, k] -> f32[k*k, C_in, C_out], cached per parameter version"""
-    w = conv.weight
-    tag = (w._version, w.data_ptr(), w.device)
-    cached = getattr(conv, "_eprecon_packed", None)
-    if cached is None or cached[0] != tag:
+    """nn.Conv2d weight [C_out, C_in, k, k] -> f32[k*k, C_in, C_out] (cached: weight_cache)"""
+    w = conv._parameters["weight"]
+
+    def build():
         co, ci, kh, kw = w.shape
         assert kh == kw and kh % 2 == 1 and conv.stride == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1
-        cached = (tag, w.detach().permute(2, 3, 1, 0).reshape(kh * kw, ci, co).contiguous())
-        conv._eprecon_packed = cached
-    return cached[1]
+        return w.detach().permute(2, 3, 1, 0).reshape(kh * kw, ci, co).contiguous()
+    return weight_cache.derived(conv, "dense2d.packed_weight", (w,), build)
 
 
 # 3x3 layers on long pixel lists through the direct gather kernel (csrc/sparse_conv_direct_kernels.hpp) on the pixel map instead of the

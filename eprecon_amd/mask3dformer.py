@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, weight_cache
 from . import sparse as SP
 
 
@@ -220,8 +220,6 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
         # EPRECON_DECODER_FUSED=0: the decoder on PyTorch ops (key / value projections, SDPA over a dense [Q, N] mask, the query
         # side replayed from HIP graphs) instead of the HIP kernels of csrc/decoder.hip
         self.use_fused_voxel_side = __import__("os").environ.get("EPRECON_DECODER_FUSED", "1") == "1"
-        self._plan = None
-        self._plan_params = None
 
     def get_pos_encs(self, coords, spitial_shape):
         out = []
@@ -267,23 +265,16 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
         q_next = self._project_q(j + 1, output, query_embed) if j + 1 < self.num_layers else None
         return output, cls, me, q_next
 
-    def _apply(self, fn, *args, **kwargs):
-        self._plan_params = None        # .to() / .cuda() may replace the parameter objects
-        return super()._apply(fn, *args, **kwargs)
-
     def _static_plan(self, device):
         """Inference on the GPU: the query side of every layer captured once into a HIP graph (7 small GEMMs, two
         LayerNorms, an 80 x 80 attention, ... per layer -> one replay), chained through static tensors; re-captured
-        when a parameter changes.  Returns None when graphs cannot be used (CPU, autograd)."""
+        when a parameter changes (cached: weight_cache).  Returns None when graphs cannot be used (CPU, autograd)."""
         if device.type != "cuda" or torch.is_grad_enabled() or not self.use_hip_graph:
             return None
-        params = self._plan_params          # (self.parameters() walks the module tree: 0.6 ms per call on 150 modules)
-        if params is None:
-            params = self._plan_params = list(self.parameters())
-        key = (device, tuple(p._version for p in params), tuple(p.data_ptr() for p in params))
-        plan = self._plan
-        if plan is not None and plan["key"] == key:
-            return plan
+        return weight_cache.derived(self, "mask3dformer.static_plan", weight_cache.parameter_sources(self),
+                                    lambda: self._capture_plan(device))
+
+    def _capture_plan(self, device):
         qe = self.query_embed.weight.unsqueeze(1)
         attn0 = self.transformer_cross_attention_layers[0].multihead_attn
         h, c = attn0.num_heads, attn0.embed_dim
@@ -303,9 +294,7 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
                 state, cls, me, q_next = self._query_side(j, o_in[j], state, qe)
             layers.append({"graph": g, "o_in": o_in[j], "cls": cls, "me": me, "q_next": q_next})
-        plan = {"key": key, "cls0": cls0, "me0": me0, "q0": q0, "layers": layers}
-        self._plan = plan
-        return plan
+        return {"cls0": cls0, "me0": me0, "q0": q0, "layers": layers}
 
     def _mask_and_block(self, me, mask_features, mask_indices):
         """mask logits [1, Q, N2] of a prediction head and the attention mask bool[Q, N_level] (True = blocked)"""
@@ -314,16 +303,13 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
         return outputs_mask, (attn.sigmoid() < 0.5).detach()
 
     def _query_side_pack(self, device):
-        """Everything the HIP query side needs, built once per parameter version: every weight matrix transposed to [in][out]
+        """Everything the HIP query side needs (cached: weight_cache): every weight matrix transposed to [in][out]
         (contiguous), the prediction head of the UNTOUCHED queries (static: models/mask3dformer.py:376-381 runs it before the
         first layer) and the first layer's projected queries."""
-        params = self._plan_params
-        if params is None:
-            params = self._plan_params = list(self.parameters())
-        key = (device, tuple(p._version for p in params), tuple(p.data_ptr() for p in params))
-        pack = getattr(self, "_qs_pack", None)
-        if pack is not None and pack["key"] == key:
-            return pack
+        return weight_cache.derived(self, "mask3dformer.query_side_pack", weight_cache.parameter_sources(self),
+                                    self._build_query_side_pack, (device,))
+
+    def _build_query_side_pack(self):
         t = lambda w: w.detach().t().contiguous()
         v = lambda x: x.detach().contiguous()
         layers = []
@@ -368,12 +354,10 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
               all(l.norm.eps == 1e-5 for l in self.transformer_ffn_layers) and
               all(l.norm.eps == 1e-5 for l in self.transformer_cross_attention_layers) and
               all(l.norm.eps == 1e-5 for l in self.transformer_self_attention_layers))
-        pack = {"key": key, "layers": layers, "kv_levels": kv_levels, "cls0": cls0.contiguous(), "me0": me0.contiguous(), "q0": q0, "ok": ok,
+        return {"layers": layers, "kv_levels": kv_levels, "cls0": cls0.contiguous(), "me0": me0.contiguous(), "q0": q0, "ok": ok,
                 "state0": self.query_feat.weight.detach().contiguous(), "qpos": self.query_embed.weight.detach().contiguous(),
                 "ffn_dim": self.transformer_ffn_layers[0].linear1.out_features, "n_cls": self.class_embed.out_features,
                 "mask_hidden": self.mask_embed.layers[0].out_features}
-        self._qs_pack = pack
-        return pack
 
     def _query_side_hip(self, pack, j, o_attn, state, outs, cls_out, ws):
         """one layer's query side on csrc/decoder.hip (two launches): -> (state, class logits [1, Q, K+1], mask embedding
@@ -398,12 +382,12 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
         q_next = None if last else outs[2].view(q_n, h, c // h).transpose(0, 1).unsqueeze(0)
         return outs[0], cls_out.unsqueeze(0), outs[1].unsqueeze(0), q_next
 
-    def _forward_fused(self, panoptic_features, panoptic_coords, mask_features, spitial_shape):
+    def _forward_fused(self, pack, panoptic_features, panoptic_coords, mask_features, spitial_shape):
         """GPU inference, every step on csrc/decoder.hip + three GEMMs per layer: the mask logits (voxel-major: [N_2, Q]), the
         key / value projections, the masked attention as ONE split-K flash-attention pass over the level's voxels, and the
         query side (static shape) as two launches.  pred_masks of the auxiliary heads are [1, Q, N_2] VIEWS of the voxel-major
-        logit matrices (same values and shape as the reference's, other strides); the final head's are contiguous."""
-        pack = self._query_side_pack(mask_features.device)
+        logit matrices (same values and shape as the reference's, other strides); the final head's are contiguous.
+        pack: _query_side_pack's (its tag reads every parameter: once per pass)"""
         c = self.query_feat.weight.shape[1]
         heads = self.num_heads
         n_q = self.num_queries
@@ -454,8 +438,10 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
             c = self.query_feat.weight.shape[1]
             ffn = self.transformer_ffn_layers[0].linear1.out_features
             if (c // self.num_heads == 6 and self.num_heads % 2 == 0 and self.num_heads <= 8 and c <= 64 and self.num_queries <= 128
-                    and ffn <= 256 and self.mask_embed.layers[0].out_features <= 256 and self._query_side_pack(mask_features.device)["ok"]):
-                return self._forward_fused(panoptic_features, panoptic_coords, mask_features, spitial_shape)
+                    and ffn <= 256 and self.mask_embed.layers[0].out_features <= 256):
+                pack = self._query_side_pack(mask_features.device)
+                if pack["ok"]:
+                    return self._forward_fused(pack, panoptic_features, panoptic_coords, mask_features, spitial_shape)
         pos = self.get_pos_encs(panoptic_coords, spitial_shape)
         src, sizes = [], []
         for i in range(self.num_feature_levels):

@@ -26,6 +26,7 @@ import torch.nn.functional as F
 from . import autograd as AG
 from . import dense2d as D2
 from . import sparse as SP
+from . import weight_cache
 
 
 def recording():
@@ -522,14 +523,10 @@ __all__ = ["SPVCNN", "SConv3d", "ConvGRU"]
 
 
 def _linear_wt(lin):
-    """weight of an nn.Linear as the [C_in, C_out] matrix the per-voxel GEMM takes, transposed once per weight
-    version (the inference path calls every layer thousands of times with the same weights)"""
-    hit = getattr(lin, "_wt_cache", None)
-    tag = (lin.weight._version, lin.weight.data_ptr())
-    if hit is None or hit[0] != tag or hit[1].device != lin.weight.device:
-        hit = (tag, lin.weight.detach().t().contiguous())
-        lin._wt_cache = hit
-    return hit[1]
+    """weight of an nn.Linear as the [C_in, C_out] matrix the per-voxel GEMM takes (cached: weight_cache — the inference path
+    calls every layer thousands of times with the same weights)"""
+    w = lin._parameters["weight"]
+    return weight_cache.derived(lin, "modules.linear_wt", (w,), lambda: w.detach().t().contiguous())
 
 
 class Conv3d(nn.Module):
@@ -691,10 +688,6 @@ class SPVCNN(nn.Module):
         z3 = voxel_to_point(SparseTensor(f, s1), z1, out=self.point_transforms[1].run(z1.F), accumulate=True)
         return z3.F
 
-    def _apply(self, fn, *args, **kwargs):
-        self._native_params = self._native = None      # .to() / .cuda() may replace the parameter objects
-        return super()._apply(fn, *args, **kwargs)
-
     def _native_slots(self):
         """(conv modules, BatchNorm modules) in the slot order of eprecon_spvcnn_forward_desc"""
         convs, bns = [], []
@@ -717,22 +710,15 @@ class SPVCNN(nn.Module):
         convs.append(_linear_wt(self.point_transforms[1][0])); bns.append(self.point_transforms[1][1])
         return convs, bns
 
-    def _native_desc(self, device):
-        """the static part of eprecon_spvcnn_forward_desc (weights, their operand-order packings, BatchNorm parameters), built
-        once per parameter version"""
+    def native_ready(self):
+        """whether the one-call pass has its descriptor: built by a forward, not dropped since"""
+        return weight_cache.peek(self, "modules.spvcnn_native") is not None
+
+    def _native_desc(self):
+        """the static part of eprecon_spvcnn_forward_desc (weights, their operand-order packings, BatchNorm parameters), or None"""
         from . import _lib
-        slots = getattr(self, "_native_params", None)
-        if slots is None:       # (walking the module tree costs ~0.25 ms per call: once; what is kept is WHERE the parameters
-            # live — each submodule's _parameters dict + name —, so a Parameter object replaced later (load_state_dict(assign=True),
-            # `module.weight = nn.Parameter(..)`) is seen by the key below: ADVICE r05)
-            slots = self._native_params = [(m._parameters, n) for m in self.modules() for n in m._parameters if m._parameters[n] is not None]
-        key = (device, tuple((id(p_), p_._version, p_.data_ptr()) for p_ in (d_[n] for d_, n in slots)))
-        hit = getattr(self, "_native", None)
-        if hit is not None and hit[0] == key:
-            return hit[1]
         convs, bns = self._native_slots()
         if len(convs) != _lib.SPVCNN_CONVS:       # (a channel plan whose residual blocks lost / gained a 1x1 skip: Python path)
-            self._native = (key, None)
             return None
         d, keep = _lib.SpvcnnForwardDesc(), []
         with torch.no_grad():
@@ -756,8 +742,7 @@ class SPVCNN(nn.Module):
                 b = d.bn[slot]
                 b.gamma, b.beta, b.eps = bn.weight.data_ptr(), bn.bias.data_ptr(), float(bn.eps)
         d.cs[:] = self.cs
-        self._native = (key, (d, keep))
-        return self._native[1]
+        return d, keep
 
     def _forward_native(self, z):
         """SPVCNN.forward as ONE library call on the voxelisation of z (found in / entered into the cache like initial_voxelize
@@ -768,7 +753,7 @@ class SPVCNN(nn.Module):
         feat = z.F
         if feat.dtype != torch.float32 or feat.stride(1) != 1:
             return None
-        pack = self._native_desc(feat.device)
+        pack = weight_cache.derived(self, "modules.spvcnn_native", weight_cache.parameter_sources(self), self._native_desc)
         if pack is None:
             return None
         d, _keep = pack
@@ -922,11 +907,12 @@ class ConvGRU(nn.Module):
         return h.F
 
     def _merged_skip(self):
+        """([c_in, 2 c] weight, [2 c] bias) of convz's and convr's point-wise skips side by side (cached: weight_cache)"""
         lz, lr = self.convz.point_transforms[0], self.convr.point_transforms[0]
-        tag = tuple((t._version, t.data_ptr()) for t in (lz.weight, lr.weight, lz.bias, lr.bias))
-        hit = getattr(self, "_wt_cache", None)
-        if hit is None or hit[0] != tag:
+        pz, pr = lz._parameters, lr._parameters
+        wz, wr, bz, br = pz["weight"], pr["weight"], pz["bias"], pr["bias"]
+
+        def build():
             with torch.no_grad():
-                hit = (tag, torch.cat([lz.weight.t(), lr.weight.t()], dim=1).contiguous(), torch.cat([lz.bias, lr.bias]).contiguous())
-            self._wt_cache = hit
-        return hit[1], hit[2]
+                return torch.cat([wz.t(), wr.t()], dim=1).contiguous(), torch.cat([bz, br]).contiguous()
+        return weight_cache.derived(self, "modules.merged_skip", (wz, wr, bz, br), build)

@@ -11,7 +11,7 @@ import threading
 
 import torch
 
-from . import _lib
+from . import _lib, weight_cache
 
 
 class IdentityCache:
@@ -237,19 +237,26 @@ class DenseMap:
 
 # Every packing made from a weight tensor's own storage is remembered here (weak reference to the tensor object the cache lives
 # on): repack_registered() rebuilds them all in ONE launch after an optimizer step (TrainStep.run) instead of one launch per
-# layer at its next use — ~190 launches per step.  id(owner) -> {kind: (weakref, shape)}
+# layer at its next use — ~190 launches per step.  (id(owner), slot) -> (weakref, shape, the cache entry's extra)
 _PACK_REGISTRY = {}
-_PACK_TABLE = {"key": None, "jobs": None, "entries": None}
+_PACK_TABLE = {"key": None, "jobs": None}
+_PACK, _PACK16 = "sparse.packed_weight", "sparse.packed_weight16"     # slots of weight_cache; the library's kinds 0 and 1
 
 
-def _register_pack(owner, kind, shape, source_ptr):
+def _pack(weight, owner, slot, extra=()):
+    """the build step of packed_weight / packed_weight16: one packing launch, registered for repack_registered"""
     import weakref
-    if source_ptr != owner.data_ptr():      # packed from a temporary contiguous copy: nothing a later launch could re-read
-        return
-    slot = _PACK_REGISTRY.setdefault(id(owner), {})
-    if kind not in slot or slot[kind][0]() is not owner or slot[kind][1] != tuple(shape):
-        slot[kind] = (weakref.ref(owner), tuple(shape))
-        _PACK_TABLE["key"] = None
+    lib = _lib.load()
+    name = "eprecon_conv_pack_weight16" if slot == _PACK16 else "eprecon_conv_pack_weight"
+    kvol, cin, cout = weight.shape
+    w = weight.detach().contiguous()
+    packed = torch.empty(int(getattr(lib, name + "_floats")(kvol, cin, cout)), dtype=torch.float32, device=weight.device)
+    _lib.check(getattr(lib, name + "_async")(_lib.ptr(w), kvol, cin, cout, _lib.ptr(packed), _lib.current_stream()), name + "_async")
+    if w.data_ptr() == owner.data_ptr():
+        _PACK_REGISTRY[(id(owner), slot)] = (weakref.ref(owner), (kvol, cin, cout), extra)
+    else:       # packed from a temporary contiguous copy: nothing a later launch could re-read
+        _PACK_REGISTRY.pop((id(owner), slot), None)
+    return packed
 
 
 def repack_registered():
@@ -257,77 +264,44 @@ def repack_registered():
     them all), in one launch on the current stream; the caches' tags follow, so the layers' next packed_weight /
     packed_weight16 calls are hits.  Tensors that were freed, moved or re-shaped drop out of the registry.  -> jobs launched"""
     import numpy as np
-    entries = []
-    for oid in list(_PACK_REGISTRY):
-        slot = _PACK_REGISTRY[oid]
-        for kind in list(slot):
-            ref, shape = slot[kind]
-            owner = ref()
-            hit = getattr(owner, "_d3_pack" if kind == 0 else "_d3_pack16", None) if owner is not None else None
-            if owner is None or hit is None or not owner.is_cuda or (kind == 1 and hit[0][2] != shape):
-                del slot[kind]
-                _PACK_TABLE["key"] = None
-                continue
-            entries.append((owner, kind, shape, hit[1]))
-        if not slot:
-            del _PACK_REGISTRY[oid]
-    stale = [e for e in entries if (e[0]._version, e[0].data_ptr()) != getattr(e[0], "_d3_pack" if e[1] == 0 else "_d3_pack16")[0][:2]]
+    stale = []
+    for key, (ref, shape, extra) in list(_PACK_REGISTRY.items()):
+        owner, slot = ref(), key[1]
+        packed = weight_cache.peek(owner, slot) if owner is not None else None
+        if packed is None or not owner.is_cuda:
+            del _PACK_REGISTRY[key]
+        elif not weight_cache.current(owner, slot, (owner,), extra):
+            stale.append((owner, slot, shape, packed, extra))
     if not stale:
         return 0
-    key = tuple((o.data_ptr(), k, s, p.data_ptr()) for o, k, s, p in stale)
+    key = tuple((o.data_ptr(), k, s, p.data_ptr()) for o, k, s, p, _ in stale)
     if _PACK_TABLE["key"] != key:     # (the table is uploaded once: pointers and shapes do not change from step to step)
         job = np.zeros(len(stale), dtype=np.dtype([("weight", "<u8"), ("packed", "<u8"), ("kvol", "<i4"), ("cin", "<i4"),
                                                    ("cout", "<i4"), ("kind", "<i4")]))
-        for i, (o, k, s, p) in enumerate(stale):
-            job[i] = (o.data_ptr(), p.data_ptr(), s[0], s[1], s[2], k)
+        for i, (o, k, s, p, _) in enumerate(stale):
+            job[i] = (o.data_ptr(), p.data_ptr(), s[0], s[1], s[2], int(k == _PACK16))
         _PACK_TABLE["jobs"] = torch.from_numpy(job.view(np.uint8).copy()).to(stale[0][0].device)
         _PACK_TABLE["key"] = key
     lib = _lib.load()
     _lib.check(lib.eprecon_conv_pack_many_async(_lib.ptr(_PACK_TABLE["jobs"]), len(stale), _lib.current_stream()),
                "eprecon_conv_pack_many_async")
-    for o, k, s, p in stale:
-        if k == 0:
-            o._d3_pack = ((o._version, o.data_ptr()), p)
-        else:
-            o._d3_pack16 = ((o._version, o.data_ptr(), s), p)
+    for o, k, _, _, extra in stale:
+        weight_cache.retag(o, k, (o,), extra)
     return len(stale)
 
 
 def packed_weight(weight):
-    """`weight` f32[27, Cin, Cout] in the operand order of the dense-grid kernel, packed once per weight version"""
-    hit = getattr(weight, "_d3_pack", None)
-    tag = (weight._version, weight.data_ptr())
-    if hit is None or hit[0] != tag or hit[1].device != weight.device:
-        lib = _lib.load()
-        kvol, cin, cout = weight.shape
-        w = weight.detach().contiguous()
-        packed = torch.empty(int(lib.eprecon_conv_pack_weight_floats(kvol, cin, cout)), dtype=torch.float32, device=weight.device)
-        _lib.check(lib.eprecon_conv_pack_weight_async(_lib.ptr(w), kvol, cin, cout, _lib.ptr(packed), _lib.current_stream()),
-                   "eprecon_conv_pack_weight_async")
-        hit = (tag, packed)
-        weight._d3_pack = hit
-        _register_pack(weight, 0, (kvol, cin, cout), w.data_ptr())
-    return hit[1]
+    """`weight` f32[27, Cin, Cout] in the operand order of the dense-grid kernel (cached: weight_cache)"""
+    return weight_cache.derived(weight, _PACK, (weight,), lambda: _pack(weight, weight, _PACK))
 
 
 def packed_weight16(weight, owner=None):
     """`weight` f32[K, Cin, Cout <= 80] in the operand order of the 16x16x4 MFMA kernels (16-row tile kernel, direct gather
-    kernel), packed once per weight version.  owner: the tensor OBJECT the packing is cached on when `weight` is a transient
+    kernel) (cached: weight_cache).  owner: the tensor OBJECT the packing is cached on when `weight` is a transient
     view of it (a [Cin, Cout] matrix unsqueezed to K = 1)"""
     owner = weight if owner is None else owner
-    hit = getattr(owner, "_d3_pack16", None)
-    tag = (owner._version, owner.data_ptr(), tuple(weight.shape))
-    if hit is None or hit[0] != tag or hit[1].device != weight.device:
-        lib = _lib.load()
-        kvol, cin, cout = weight.shape
-        w = weight.detach().contiguous()
-        packed = torch.empty(int(lib.eprecon_conv_pack_weight16_floats(kvol, cin, cout)), dtype=torch.float32, device=weight.device)
-        _lib.check(lib.eprecon_conv_pack_weight16_async(_lib.ptr(w), kvol, cin, cout, _lib.ptr(packed), _lib.current_stream()),
-                   "eprecon_conv_pack_weight16_async")
-        hit = (tag, packed)
-        owner._d3_pack16 = hit
-        _register_pack(owner, 1, (kvol, cin, cout), w.data_ptr())
-    return hit[1]
+    shape = tuple(weight.shape)
+    return weight_cache.derived(owner, _PACK16, (owner,), lambda: _pack(weight, owner, _PACK16, shape), shape)
 
 
 def voxel_hierarchy(vox, levels=3, points=None):
@@ -388,18 +362,9 @@ def _hierarchy_with_geometry(vox, points, grids, uniqs, invs, sizes):
 
 
 def clear_packed_weights(module):
-    """Drop every operand-order copy cached on the parameters / layers of `module` (packed_weight, packed_weight16,
-    dense2d.packed_weight, modules._linear_wt, SPVCNN's native-pass descriptor).  The caches are keyed on (tensor version, data_ptr): writes through `p.data`
-    (dist.broadcast(p.data, ...), EMA swaps, manual loaders) change neither — call this after them."""
-    for p_ in module.parameters():
-        for attr in ("_d3_pack", "_d3_pack16"):
-            if hasattr(p_, attr):
-                delattr(p_, attr)
-    for m in module.modules():
-        # (_native / _native_params: SPVCNN's descriptor of the one-call pass, which holds packed copies of all of the above)
-        for attr in ("_wt_cache", "_eprecon_packed", "_eprecon_merged", "_native", "_native_params"):
-            if hasattr(m, attr):
-                delattr(m, attr)
+    """Drop every weight-derived copy cached on `module`, its submodules and their parameters: the contract after a write
+    through `p.data` (weight_cache has the rule)"""
+    weight_cache.clear(module)
 
 
 # point-wise layers (K = 1) on lists at least this long take the direct kernel too (a streaming [N, C_in] x [C_in, C_out <= 64]
@@ -783,26 +748,23 @@ def mlp4x_supported(channels, out_channels):
 
 
 def pack_mlp4x(mod):
-    """the parameters of a Linear4xTrans in the kernel's operand order, ONE flat buffer (cached on the module per weight
-    version; clear_packed_weights drops it) -> dict name -> tensor view"""
-    params = (mod.linear1.weight, mod.linear1.bias, mod.norm1.weight, mod.norm1.bias, mod.linear2.weight, mod.linear2.bias,
-              mod.norm2.weight, mod.norm2.bias, mod.linear3.weight, mod.linear3.bias)
-    tag = tuple((p_._version, p_.data_ptr()) for p_ in params)
-    hit = getattr(mod, "_eprecon_packed", None)
-    if hit is not None and hit[0] == tag:
-        return hit[1]
-    with torch.no_grad():
-        parts = {"w1": _pack_mlp_weight(mod.linear1.weight.t()), "b1": _pad16(mod.linear1.bias), "g1": _pad16(mod.norm1.weight),
-                 "be1": _pad16(mod.norm1.bias), "w2": _pack_mlp_weight(mod.linear2.weight.t()), "b2": _pad16(mod.linear2.bias),
-                 "g2": _pad16(mod.norm2.weight), "be2": _pad16(mod.norm2.bias), "w3": _pack_mlp_weight(mod.linear3.weight.t()),
-                 "b3": _pad16(mod.linear3.bias)}
-        flat = torch.cat([v for v in parts.values()])        # (every part is a multiple of 16 floats: 16-byte aligned views)
-        views, off = {}, 0
-        for name, v in parts.items():
-            views[name] = flat[off:off + v.numel()]
-            off += v.numel()
-    mod._eprecon_packed = (tag, views)
-    return views
+    """the parameters of a Linear4xTrans in the kernel's operand order, ONE flat buffer (cached: weight_cache)
+    -> dict name -> tensor view"""
+    l1, n1, l2, n2, l3 = mod.linear1, mod.norm1, mod.linear2, mod.norm2, mod.linear3
+
+    def build():
+        with torch.no_grad():
+            parts = {"w1": _pack_mlp_weight(l1.weight.t()), "b1": _pad16(l1.bias), "g1": _pad16(n1.weight), "be1": _pad16(n1.bias),
+                     "w2": _pack_mlp_weight(l2.weight.t()), "b2": _pad16(l2.bias), "g2": _pad16(n2.weight), "be2": _pad16(n2.bias),
+                     "w3": _pack_mlp_weight(l3.weight.t()), "b3": _pad16(l3.bias)}
+            flat = torch.cat([v for v in parts.values()])        # (every part is a multiple of 16 floats: 16-byte aligned views)
+            views, off = {}, 0
+            for name, v in parts.items():
+                views[name] = flat[off:off + v.numel()]
+                off += v.numel()
+        return views
+    return weight_cache.derived(mod, "sparse.pack_mlp4x", (l1.weight, l1.bias, n1.weight, n1.bias, l2.weight, l2.bias, n2.weight,
+                                                           n2.bias, l3.weight, l3.bias), build)
 
 
 def mlp4x(mods, x, outs=None):

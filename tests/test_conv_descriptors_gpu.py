@@ -368,6 +368,7 @@ def test_packing_of_a_2d_weight_is_cached_on_its_owner():
     """a [Cin, Cout] weight becomes a transient [1, Cin, Cout] view in the wrapper: its packing must be found again through
     the object the caller holds"""
     from eprecon_amd import sparse as SP
+    from eprecon_amd import weight_cache
     rng = np.random.default_rng(5)
     o = operands(rng, 1000, 1000, 1, 32, 64, wdim=2)
     with Patched(), Recorder() as rec:
@@ -378,7 +379,7 @@ def test_packing_of_a_2d_weight_is_cached_on_its_owner():
         torch.cuda.synchronize()
     assert first == 1 and rec.packs16 == 1
     assert all("packed_weight16" in s["launches"][0]["pointers"] for s in rec.steps)
-    assert hasattr(o["w"], "_d3_pack16")
+    assert weight_cache.peek(o["w"], "sparse.packed_weight16") is not None
 
 
 def record(commit, path):

@@ -268,3 +268,53 @@ def test_query_side_kernels_match_the_torch_modules(j):
         assert ref_q is None and got_q is None
     else:
         assert got_q.shape == ref_q.shape and float((got_q - ref_q).abs().max()) < 5e-5
+
+
+@pytest.mark.gpu
+def test_decoder_follows_rewritten_and_replaced_weights(golden_dir):
+    """The decoder keeps copies of its weights (the fused path's transposed matrices and static first head, the graph path's
+    captured query side).  After (a) a write through `p.data` + sparse.clear_packed_weights and (b) replaced Parameter objects
+    (load_state_dict(assign=True), no clear call), both must agree with the PyTorch-module path of the same decoder, which
+    reads the live weights, within the tolerances of test_fused_voxel_side_equals_the_dense_path_at_cfg4_size, and must differ
+    from their own result before the change by ten times those.  (The decoder is the cfg4 one on the small inputs: the
+    16-channel decoder of test_decoder_matches_reference_golden has 4 channels per head, which the fused path does not take.)"""
+    from eprecon_amd import weight_cache
+    from eprecon_amd.mask3dformer import MultiScaleMaskedTransformerDecoder
+    from eprecon_amd.sparse import clear_packed_weights
+    gold = np.load(os.path.join(golden_dir, "mask3dformer_at_size.npz"))
+    dec = MultiScaleMaskedTransformerDecoder(mask_classification=True, num_classes=20, hidden_dim=48, num_queries=80,
+                                             nheads=8, dim_feedforward=192, dec_layers=6, pre_norm=False, mask_dim=48)
+    dec.load_state_dict({k[4:]: torch.from_numpy(gold[k]) for k in gold.files if k.startswith("sd__")}, strict=True)
+    dec = dec.cuda()
+    coords, feats, mask_feat = mask3d_inputs(c=48)
+    args = ([torch.from_numpy(f).cuda() for f in feats], [torch.from_numpy(c)[None].cuda() for c in coords],
+            torch.from_numpy(mask_feat).cuda(), (40, 40, 40))
+    tol = {"pred_logits": 5e-4, "pred_masks": 1e-3}
+
+    def run(fused, graph):
+        dec.use_fused_voxel_side, dec.use_hip_graph = fused, graph
+        with torch.no_grad():
+            out = dec(*args)
+        return {k: out[k].clone() for k in tol}
+
+    def step(before=None):
+        got = {"fused": run(True, False), "graph": run(False, True)}
+        assert weight_cache.peek(dec, "mask3dformer.query_side_pack") is not None       # the paths meant did run
+        assert weight_cache.peek(dec, "mask3dformer.static_plan") is not None
+        live = run(False, False)
+        for path, out in got.items():
+            for k, t in tol.items():
+                err = float((out[k] - live[k]).abs().max())
+                moved = None if before is None else float((out[k] - before[path][k]).abs().max())
+                print(f"{path} {k}: against the live weights {err:.3g}, against its result before the change {moved}")
+                assert err < t, (path, k, err)
+                assert moved is None or moved >= 10 * t, (path, k, moved)
+        return got
+
+    first = step()
+    for p in dec.parameters():                  # (a) neither the version counter nor the pointer moves
+        p.data.mul_(1.25)
+    clear_packed_weights(dec)
+    second = step(first)
+    dec.load_state_dict({k: v * 0.5 for k, v in dec.state_dict().items()}, assign=True)      # (b) new objects, no clear call
+    step(second)

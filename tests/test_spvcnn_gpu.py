@@ -93,7 +93,7 @@ def test_spvcnn_matches_oracle(stage, cin, n):
         out = net(PointTensor(dev(feat), dev(pts))).cpu().numpy()
         # the pass issued by ONE library call (default) and launch by launch from Python: the same launches, bit for bit
         import eprecon_amd.modules as M
-        assert M._NATIVE_SPVCNN and net._native[1] is not None
+        assert M._NATIVE_SPVCNN and net.native_ready()
         M._NATIVE_SPVCNN = False
         try:
             py = net(PointTensor(dev(feat), dev(pts))).cpu().numpy()
@@ -123,7 +123,7 @@ def test_native_pass_follows_weight_rewrites():
     def both():
         with torch.no_grad():
             nat = net(PointTensor(dev(feat), dev(pts))).cpu().numpy()
-            assert net._native[1] is not None
+            assert net.native_ready()
             M._NATIVE_SPVCNN = False
             try:
                 py = net(PointTensor(dev(feat), dev(pts))).cpu().numpy()
