@@ -67,17 +67,14 @@ SIGNATURES = {
     "eprecon_conv_desc_takes_bn_acc": (_i, [_vp]),
     "eprecon_batchnorm_acc_affine_async": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp]),
     "eprecon_affine_rows_acc_async": (_i, [_vp, _i64, _i, _i, _vp, _i, _i, _f, _i, _vp, _i, _vp]),
-    "eprecon_affine_rows_res_async": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp]),
     "eprecon_batchnorm_finalize_affine_async": (_i, [_vp, _i64, _i64, _i, _vp, _vp, _f, _vp, _vp, _vp]),
-    "eprecon_affine_rows_async": (_i, [_vp, _i64, _i, _i, _vp, _vp, _i, _vp, _i, _vp]),
+    "eprecon_affine_rows_async": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp]),
     "eprecon_affine_pool2_rows_async": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp]),
     "eprecon_affine_up2_rows_async": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp]),
     "eprecon_pixel_map_async": (_i, [_i, _i, _i, _i, _vp, _vp]),
     "eprecon_batchnorm_apply_workspace_bytes": (_sz, [_i]),
-    "eprecon_batchnorm_apply_partials_async": (_i, [_vp, _i64, _i, _i, _vp, _i64, _i64, _vp, _vp, _f, _vp, _i, _i, _vp, _i,
-                                                    _vp, _vp, _vp, _sz, _vp]),
-    "eprecon_batchnorm_apply_partials_res_async": (_i, [_vp, _i64, _i, _i, _vp, _i64, _i64, _vp, _vp, _f, _vp, _i, _vp, _vp, _i,
-                                                        _vp, _i, _vp, _sz, _vp]),
+    "eprecon_batchnorm_apply_partials_async": (_i, [_vp, _i64, _i, _i, _vp, _i64, _i64, _vp, _vp, _f, _vp, _i, _vp, _vp, _i,
+                                                    _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "eprecon_batchnorm_workspace_bytes": (_sz, [_i64, _i]),
     "eprecon_batchnorm_train_async": (_i, [_vp, _i64, _i, _i, _vp, _vp, _f, _vp, _i, _i, _vp, _i, _vp, _vp,
                                            _vp, _sz, _vp]),
@@ -222,7 +219,7 @@ SIGNATURES = {
 VIEWS_TILE_H, VIEWS_MAX_KSIZE = 16, 9
 
 EPRECON_OK, EPRECON_EMPTY = 0, 1
-ABI_VERSION = 1
+ABI_VERSION = 2
 
 
 class EpreconError(RuntimeError):

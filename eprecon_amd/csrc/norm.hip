@@ -10,28 +10,16 @@
 // Bandwidth-bound column / row reductions; deterministic (fixed-order Chan merges, no float atomics).
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.hpp"
 #include "conv_common.hpp"
 
 namespace {
 using namespace ep;
+using epconv::chan_merge;  // the producers' summaries and the finalize merge with the same function
 
 constexpr int kBnPerThread = 8;  // rows each thread of the statistics kernel keeps in registers
-
-// Chan et al. merge of two (count, mean, M2) summaries — exact up to rounding, order fixed by the caller
-__device__ __forceinline__ void chan_merge(float &n_a, float &mean_a, float &m2_a, float n_b, float mean_b, float m2_b)
-{
-    if (n_b == 0.0f) return;
-    if (n_a == 0.0f) {
-        n_a = n_b; mean_a = mean_b; m2_a = m2_b;
-        return;
-    }
-    const float n = n_a + n_b;
-    const float d = mean_b - mean_a;
-    mean_a = mean_a + d * (n_b / n);
-    m2_a = m2_a + m2_b + d * d * (n_a * n_b / n);
-    n_a = n;
-}
 
 // One pass over x: block b summarises rows [b*R, (b+1)*R) with R = kBnPerThread * (256 / C); every
 // thread owns one column and <= 8 rows held in registers (two-pass mean / M2 on those, no
@@ -119,6 +107,19 @@ inline int bn_finalize_nu(int64_t nblk)
     return need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : need <= 8 ? 8 : 16;
 }
 
+// ... as a compile-time NU: launch(std::integral_constant<int, NU>) picks the instantiation of a kernel template
+template <class Launch>
+void with_finalize_nu(int64_t nblk, Launch launch)
+{
+    switch (bn_finalize_nu(nblk)) {
+    case 1: launch(std::integral_constant<int, 1>()); break;
+    case 2: launch(std::integral_constant<int, 2>()); break;
+    case 4: launch(std::integral_constant<int, 4>()); break;
+    case 8: launch(std::integral_constant<int, 8>()); break;
+    default: launch(std::integral_constant<int, 16>()); break;
+    }
+}
+
 // one workgroup per channel: thread t merges partials t, t+256, ... in order, then a fixed LDS tree
 template <int NU>
 __global__ __launch_bounds__(256) void bn_finalize_kernel(const float *partial, int nblk, int64_t ld, int C, float *mean_out,
@@ -180,17 +181,15 @@ __global__ __launch_bounds__(256) void bn_finalize_affine_kernel(const float *pa
     }
 }
 
+// THE apply expression, element (r, c): (x - mean) * inv * gamma + beta [+ res (* res_scale + res_shift)] [relu].  The two-launch
+// and the one-launch form (bn_apply_kernel, bn_merge_apply_kernel) give the same bits because both evaluate this.
 // res_scale / res_shift (optional): the residual operand carries a pending BatchNorm of its own in affine form (the 1x1 skip
-// convolution of a residual block, models/modules.py:57-65), applied on load
-__global__ __launch_bounds__(256) void bn_apply_kernel(const float *x, int n, int C, int ld_x,
-                                                       const float *mean, const float *var,
-                                                       const float *gamma, const float *beta, float eps,
-                                                       const float *res, int ld_res, const float *res_scale,
-                                                       const float *res_shift, int relu, float *out, int ld_out)
+// convolution of a residual block, models/modules.py:57-65), applied on load.  (Plain arguments: with the launch-wide operands
+// handed to the kernels as one struct the apply launch of 93,512 x 32 rows took 0.3 us more, profiles/r27.)
+__device__ __forceinline__ float bn_apply_value(const float *x, int ld_x, int r, int c, const float *mean, const float *var,
+                                                const float *gamma, const float *beta, float eps, const float *res, int ld_res,
+                                                const float *res_scale, const float *res_shift, int relu)
 {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (size_t)n * C) return;
-    const int r = (int)(e / C), c = (int)(e - (size_t)r * C);
     const float inv = 1.0f / sqrtf(var[c] + eps);
     float v = (x[(size_t)r * ld_x + c] - mean[c]) * inv;
     v = v * (gamma ? gamma[c] : 1.0f) + (beta ? beta[c] : 0.0f);
@@ -200,7 +199,19 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float *x, int n, in
         v += rv;
     }
     if (relu) v = fmaxf(v, 0.0f);
-    out[(size_t)r * ld_out + c] = v;
+    return v;
+}
+
+__global__ __launch_bounds__(256) void bn_apply_kernel(const float *x, int n, int C, int ld_x,
+                                                       const float *mean, const float *var,
+                                                       const float *gamma, const float *beta, float eps,
+                                                       const float *res, int ld_res, const float *res_scale,
+                                                       const float *res_shift, int relu, float *out, int ld_out)
+{
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)n * C) return;
+    const int r = (int)(e / C), c = (int)(e - (size_t)r * C);
+    out[(size_t)r * ld_out + c] = bn_apply_value(x, ld_x, r, c, mean, var, gamma, beta, eps, res, ld_res, res_scale, res_shift, relu);
 }
 
 // LayerNorm over the C channels of each row: t = x; [relu]; [+ res]; LN(t) * g + b; [relu]
@@ -247,13 +258,19 @@ __global__ __launch_bounds__(256) void rowwise_ln_kernel(const float *x, int n, 
         }
 }
 
+// out = [relu]( x * scale + shift [+ res] ): a BatchNorm its producer finished.  RES is decided by the host: with a test of the
+// pointer in the kernel, the launch without a residual (dense2d.materialize, 172,800 x 24) took 9.3 - 9.4 us against 8.8 - 9.0.
+// res / ld_res come last, so that the instantiation without them finds every argument it reads where it would without them
+template <bool RES>
 __global__ __launch_bounds__(256) void affine_rows_kernel(const float *x, int n, int C, int ld_x, const float *scale,
-                                                          const float *shift, int relu, float *out, int ld_out)
+                                                          const float *shift, int relu, float *out, int ld_out,
+                                                          const float *res, int ld_res)
 {
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= (size_t)n * C) return;
     const int r = (int)(e / C), c = (int)(e - (size_t)r * C);
     float v = fmaf(x[(size_t)r * ld_x + c], scale[c], shift[c]);
+    if constexpr (RES) v += res[(size_t)r * ld_res + c];
     if (relu) v = fmaxf(v, 0.0f);
     out[(size_t)r * ld_out + c] = v;
 }
@@ -371,19 +388,6 @@ __global__ __launch_bounds__(256) void affine_rows_acc_kernel(const float *x, in
     }
 }
 
-__global__ __launch_bounds__(256) void affine_rows_res_kernel(const float *x, int n, int C, int ld_x, const float *scale,
-                                                              const float *shift, const float *res, int ld_res, int relu,
-                                                              float *out, int ld_out)
-{
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (size_t)n * C) return;
-    const int r = (int)(e / C), c = (int)(e - (size_t)r * C);
-    float v = fmaf(x[(size_t)r * ld_x + c], scale[c], shift[c]);
-    if (res) v += res[(size_t)r * ld_res + c];
-    if (relu) v = fmaxf(v, 0.0f);
-    out[(size_t)r * ld_out + c] = v;
-}
-
 // (One-launch forms for short summary lists — every workgroup finishing the statistics itself before applying them — were
 // measured twice and removed: round 3 with one wave per channel (a 10 us serial chain of Chan merges per workgroup), round 4
 // with 256 / C row groups merging side by side and the launch limited to ~16 MB of redundant summary reads: SPVCNN still lost
@@ -398,7 +402,7 @@ __global__ __launch_bounds__(256) void affine_rows_res_kernel(const float *x, in
 // merges in bn_finalize_kernel's order — rows t, t + 256, ... per thread, then the tree (t, t + 128), (t, t + 64), ... (0, 1) with
 // the lower index on the left — so mean and variance have the bits of the two-launch form: the levels 128 and 64 out of LDS by
 // wave 0, the levels 32 .. 1 as down-shuffles inside it (lane t takes lane t + s; what the lanes >= s compute is never read).
-// The rows are then normalised with bn_apply_kernel's expression.  EPRECON_INIT_GLUE=0: the two launches.
+// The rows are then normalised with bn_apply_kernel's expression (bn_apply_value).  EPRECON_INIT_GLUE=0: the two launches.
 constexpr int kBnMergeApplyMaxC = 4;
 constexpr int kBnMergeApplyBlocks = 256;    // workgroups at most: one per CU, the rows in grid strides
 
@@ -441,50 +445,68 @@ __global__ __launch_bounds__(256) void bn_merge_apply_kernel(const float *x, int
     const size_t total = (size_t)n * C;
     for (size_t e = (size_t)blockIdx.x * 256 + tid; e < total; e += (size_t)gridDim.x * 256) {
         const int r = (int)(e / C), c = (int)(e - (size_t)r * C);
-        const float inv = 1.0f / sqrtf(sStat[kBnMergeApplyMaxC + c] + eps);
-        float v = (x[(size_t)r * ld_x + c] - sStat[c]) * inv;
-        v = v * (gamma ? gamma[c] : 1.0f) + (beta ? beta[c] : 0.0f);
-        if (res) {
-            float rv = res[(size_t)r * ld_res + c];
-            if (res_scale) rv = fmaf(rv, res_scale[c], res_shift[c]);
-            v += rv;
-        }
-        if (relu) v = fmaxf(v, 0.0f);
-        out[(size_t)r * ld_out + c] = v;
+        out[(size_t)r * ld_out + c] = bn_apply_value(x, ld_x, r, c, sStat, sStat + kBnMergeApplyMaxC, gamma, beta, eps, res, ld_res,
+                                                     res_scale, res_shift, relu);
     }
 }
 
+// mean / var of a call: the caller's vectors where given, else two 256-byte-aligned runs of `channels` floats of the workspace
+struct MeanVar { float *mean, *var; };
+MeanVar carve_mean_var(void *workspace, int channels, float *mean_out, float *var_out)
+{
+    char *ws = reinterpret_cast<char *>(workspace);
+    return {mean_out ? mean_out : reinterpret_cast<float *>(ws),
+            var_out ? var_out : reinterpret_cast<float *>(ws + align_up((size_t)channels * sizeof(float), 256))};
+}
+
 int bn_finalize_apply(const float *x, int64_t n, int channels, int ld_x, const float *partial, int nblk, int64_t ld,
-                      const float *gamma, const float *beta, float eps, const float *residual, int ld_res,
-                      int relu, float *out, int ld_out, float *mean, float *var, hipStream_t st,
-                      const float *res_scale = nullptr, const float *res_shift = nullptr)
+                      const float *gamma, const float *beta, float eps, const float *residual, int ld_res, const float *res_scale,
+                      const float *res_shift, int relu, float *out, int ld_out, MeanVar mv, hipStream_t st)
 {
     if (channels <= kBnMergeApplyMaxC && !switch_off("EPRECON_INIT_GLUE")) {
         const unsigned blocks = (unsigned)ceil_div(n * channels, (int64_t)256);
         const dim3 grid(blocks < (unsigned)kBnMergeApplyBlocks ? blocks : (unsigned)kBnMergeApplyBlocks);
-        switch (bn_finalize_nu(nblk)) {
-#define EP_MERGE_APPLY(NU)                                                                                                       \
-    case NU:                                                                                                                     \
-        hipLaunchKernelGGL(bn_merge_apply_kernel<NU>, grid, dim3(256), 0, st, x, (int)n, channels, ld_x, partial, nblk, ld, gamma, \
-                           beta, eps, residual, ld_res, res_scale, res_shift, relu, out, ld_out, mean, var);                      \
-        break
-            EP_MERGE_APPLY(1); EP_MERGE_APPLY(2); EP_MERGE_APPLY(4); EP_MERGE_APPLY(8); EP_MERGE_APPLY(16);
-#undef EP_MERGE_APPLY
-        }
+        with_finalize_nu(nblk, [&](auto nu) {
+            hipLaunchKernelGGL(bn_merge_apply_kernel<decltype(nu)::value>, grid, dim3(256), 0, st, x, (int)n, channels, ld_x, partial,
+                               nblk, ld, gamma, beta, eps, residual, ld_res, res_scale, res_shift, relu, out, ld_out, mv.mean, mv.var);
+        });
         EP_LAUNCH_CHECK();
         return EPRECON_OK;
     }
-    switch (bn_finalize_nu(nblk)) {
-#define EP_FINALIZE(NU) \
-    case NU: hipLaunchKernelGGL(bn_finalize_kernel<NU>, dim3(channels), dim3(256), 0, st, partial, nblk, ld, channels, mean, var); break
-        EP_FINALIZE(1); EP_FINALIZE(2); EP_FINALIZE(4); EP_FINALIZE(8); EP_FINALIZE(16);
-#undef EP_FINALIZE
-    }
+    with_finalize_nu(nblk, [&](auto nu) {
+        hipLaunchKernelGGL(bn_finalize_kernel<decltype(nu)::value>, dim3(channels), dim3(256), 0, st, partial, nblk, ld, channels,
+                           mv.mean, mv.var);
+    });
     EP_LAUNCH_CHECK();
-    const size_t total = (size_t)n * channels;
-    hipLaunchKernelGGL(bn_apply_kernel, dim3((unsigned)ceil_div((int64_t)total, 256)), dim3(256), 0, st, x,
-                       (int)n, channels, ld_x, (const float *)mean, (const float *)var, gamma, beta, eps,
-                       residual, ld_res, res_scale, res_shift, relu, out, ld_out);
+    hipLaunchKernelGGL(bn_apply_kernel, dim3((unsigned)ceil_div(n * channels, (int64_t)256)), dim3(256), 0, st, x, (int)n, channels,
+                       ld_x, (const float *)mv.mean, (const float *)mv.var, gamma, beta, eps, residual, ld_res, res_scale, res_shift, relu,
+                       out, ld_out);
+    EP_LAUNCH_CHECK();
+    return EPRECON_OK;
+}
+
+// the joins: the same checks and the same choice between four channels per thread and one
+using JoinKernel = void (*)(const float *, int, int, int, int, int, const float *, const float *, int, float *, int);
+
+bool rows_vec4(const float *x, int ld_x, const float *out, int ld_out, int channels)
+{
+    return channels % 4 == 0 && ld_x % 4 == 0 && ld_out % 4 == 0 && ((uintptr_t)x | (uintptr_t)out) % 16 == 0;
+}
+
+// min_hw: the smallest height / width the join takes; out_rows: the rows it writes (the longer of the two lists bounds the index)
+int affine_join_rows(JoinKernel vec4, JoinKernel vec1, int min_hw, int64_t out_rows, const float *x, int maps, int height,
+                     int width, int channels, int ld_x, const float *scale, const float *shift, int relu, float *out, int ld_out,
+                     void *stream)
+{
+    if (!x || !out || !scale || !shift || maps <= 0 || height < min_hw || width < min_hw || channels <= 0 || ld_x < channels ||
+        ld_out < channels)
+        return EPRECON_ERR_ARG;
+    const int64_t in_rows = (int64_t)maps * height * width;
+    if ((in_rows > out_rows ? in_rows : out_rows) * channels > 0x7fffffffll) return EPRECON_ERR_ARG;
+    const bool v4 = rows_vec4(x, ld_x, out, ld_out, channels);
+    const dim3 grid((unsigned)ceil_div(out_rows * (channels / (v4 ? 4 : 1)), (int64_t)256));
+    hipLaunchKernelGGL(v4 ? vec4 : vec1, grid, dim3(256), 0, (hipStream_t)stream, x, maps, height, width, channels, ld_x, scale, shift,
+                       relu, out, ld_out);
     EP_LAUNCH_CHECK();
     return EPRECON_OK;
 }
@@ -517,16 +539,12 @@ int eprecon_batchnorm_train_async(const float *x, int64_t n, int channels, int l
     if (n == 0) return EPRECON_OK;
     hipStream_t st = (hipStream_t)stream;
     const int nblk = (int)ceil_div(n, bn_rows_per_block(channels));
-    char *ws = reinterpret_cast<char *>(workspace);
-    float *partial = reinterpret_cast<float *>(ws);
-    ws += align_up((size_t)nblk * 3 * channels * sizeof(float), 256);
-    float *mean = mean_out ? mean_out : reinterpret_cast<float *>(ws);
-    ws += align_up((size_t)channels * sizeof(float), 256);
-    float *var = var_out ? var_out : reinterpret_cast<float *>(ws);
+    float *partial = reinterpret_cast<float *>(workspace);
+    char *rest = reinterpret_cast<char *>(workspace) + align_up((size_t)nblk * 3 * channels * sizeof(float), 256);
     hipLaunchKernelGGL(bn_stats_kernel, dim3(nblk), dim3(256), 0, st, x, (int)n, channels, ld_x, partial);
     EP_LAUNCH_CHECK();
-    return bn_finalize_apply(x, n, channels, ld_x, partial, nblk, nblk, gamma, beta, eps, residual, ld_res, relu, out,
-                             ld_out, mean, var, st);
+    return bn_finalize_apply(x, n, channels, ld_x, partial, nblk, nblk, gamma, beta, eps, residual, ld_res, nullptr, nullptr, relu, out,
+                             ld_out, carve_mean_var(rest, channels, mean_out, var_out), st);
 }
 
 size_t eprecon_batchnorm_apply_workspace_bytes(int channels)
@@ -537,42 +555,20 @@ size_t eprecon_batchnorm_apply_workspace_bytes(int channels)
 // Second half of the train-mode BatchNorm for a tensor whose per-block (count, mean, M2) summaries
 // were already produced by its producer (eprecon_sparse_conv_fused_async's bn_partial,
 // [3][channels][ld], ld >= nblk): fixed-order merge -> mean / biased variance -> affine [+ residual] [ReLU].
-int eprecon_batchnorm_apply_partials_async(const float *x, int64_t n, int channels, int ld_x,
-                                           const float *partial, int64_t nblk, int64_t ld, const float *gamma,
-                                           const float *beta, float eps, const float *residual,
-                                           int ld_res, int relu, float *out, int ld_out, float *mean_out,
-                                           float *var_out, void *workspace, size_t workspace_bytes,
+// res_scale / res_shift: both or neither, and only with a residual (its pending BatchNorm, applied on load).
+int eprecon_batchnorm_apply_partials_async(const float *x, int64_t n, int channels, int ld_x, const float *partial, int64_t nblk,
+                                           int64_t ld, const float *gamma, const float *beta, float eps, const float *residual,
+                                           int ld_res, const float *res_scale, const float *res_shift, int relu, float *out,
+                                           int ld_out, float *mean_out, float *var_out, void *workspace, size_t workspace_bytes,
                                            void *stream)
 {
     if (!x || !out || !partial || n < 0 || nblk <= 0 || nblk > 0x7fffffff || ld < nblk || channels <= 0 || ld_x < channels ||
-        ld_out < channels || !workspace)
+        ld_out < channels || !workspace || (residual && ld_res < channels) || !res_scale != !res_shift || (res_scale && !residual))
         return EPRECON_ERR_ARG;
     if (workspace_bytes < eprecon_batchnorm_apply_workspace_bytes(channels)) return EPRECON_ERR_WORKSPACE;
     if (n == 0) return EPRECON_OK;
-    char *ws = reinterpret_cast<char *>(workspace);
-    float *mean = mean_out ? mean_out : reinterpret_cast<float *>(ws);
-    ws += align_up((size_t)channels * sizeof(float), 256);
-    float *var = var_out ? var_out : reinterpret_cast<float *>(ws);
-    return bn_finalize_apply(x, n, channels, ld_x, partial, (int)nblk, ld, gamma, beta, eps, residual, ld_res, relu,
-                             out, ld_out, mean, var, (hipStream_t)stream);
-}
-
-int eprecon_batchnorm_apply_partials_res_async(const float *x, int64_t n, int channels, int ld_x, const float *partial,
-                                               int64_t nblk, int64_t ld, const float *gamma, const float *beta, float eps,
-                                               const float *residual, int ld_res, const float *res_scale,
-                                               const float *res_shift, int relu, float *out, int ld_out, void *workspace,
-                                               size_t workspace_bytes, void *stream)
-{
-    if (!x || !out || !partial || !residual || !res_scale || !res_shift || n < 0 || nblk <= 0 || nblk > 0x7fffffff || ld < nblk ||
-        channels <= 0 || ld_x < channels || ld_out < channels || ld_res < channels || !workspace)
-        return EPRECON_ERR_ARG;
-    if (workspace_bytes < eprecon_batchnorm_apply_workspace_bytes(channels)) return EPRECON_ERR_WORKSPACE;
-    if (n == 0) return EPRECON_OK;
-    char *ws = reinterpret_cast<char *>(workspace);
-    float *mean = reinterpret_cast<float *>(ws);
-    float *var = reinterpret_cast<float *>(ws + align_up((size_t)channels * sizeof(float), 256));
-    return bn_finalize_apply(x, n, channels, ld_x, partial, (int)nblk, ld, gamma, beta, eps, residual, ld_res, relu, out, ld_out,
-                             mean, var, (hipStream_t)stream, res_scale, res_shift);
+    return bn_finalize_apply(x, n, channels, ld_x, partial, (int)nblk, ld, gamma, beta, eps, residual, ld_res, res_scale, res_shift,
+                             relu, out, ld_out, carve_mean_var(workspace, channels, mean_out, var_out), (hipStream_t)stream);
 }
 
 int eprecon_batchnorm_finalize_affine_async(const float *partial, int64_t nblk, int64_t ld, int channels, const float *gamma,
@@ -580,74 +576,42 @@ int eprecon_batchnorm_finalize_affine_async(const float *partial, int64_t nblk, 
                                             void *stream)
 {
     if (!partial || !scale_out || !shift_out || nblk <= 0 || nblk > 0x7fffffff || ld < nblk || channels <= 0) return EPRECON_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    switch (bn_finalize_nu(nblk)) {
-#define EP_FINALIZE(NU)                                                                                                            \
-    case NU:                                                                                                                       \
-        hipLaunchKernelGGL(bn_finalize_affine_kernel<NU>, dim3(channels), dim3(256), 0, st, partial, (int)nblk, ld, channels, gamma, \
-                           beta, eps, scale_out, shift_out);                                                                         \
-        break
-        EP_FINALIZE(1); EP_FINALIZE(2); EP_FINALIZE(4); EP_FINALIZE(8); EP_FINALIZE(16);
-#undef EP_FINALIZE
-    }
+    with_finalize_nu(nblk, [&](auto nu) {
+        hipLaunchKernelGGL(bn_finalize_affine_kernel<decltype(nu)::value>, dim3(channels), dim3(256), 0, (hipStream_t)stream, partial,
+                           (int)nblk, ld, channels, gamma, beta, eps, scale_out, shift_out);
+    });
     EP_LAUNCH_CHECK();
     return EPRECON_OK;
 }
 
-int eprecon_affine_rows_async(const float *x, int64_t n, int channels, int ld_x, const float *scale,
-                              const float *shift, int relu, float *out, int ld_out, void *stream)
+// out = [relu]( x * scale + shift [+ residual] ): the materialising consumer of a pending BatchNorm, and the tail of the residual
+// blocks (models/modules.py:46-72); residual may be null; out may alias x
+int eprecon_affine_rows_async(const float *x, int64_t n, int channels, int ld_x, const float *scale, const float *shift,
+                              const float *residual, int ld_res, int relu, float *out, int ld_out, void *stream)
 {
     if (!x || !out || !scale || !shift || n < 0 || channels <= 0 || ld_x < channels || ld_out < channels ||
-        n * channels > 0x7fffffffll * 256)
+        (residual && ld_res < channels) || n * channels > 0x7fffffffll * 256)
         return EPRECON_ERR_ARG;
     if (n == 0) return EPRECON_OK;
-    hipLaunchKernelGGL(affine_rows_kernel, dim3((unsigned)ceil_div(n * channels, (int64_t)256)), dim3(256), 0,
-                       (hipStream_t)stream, x, (int)n, channels, ld_x, scale, shift, relu, out, ld_out);
+    hipLaunchKernelGGL(residual ? affine_rows_kernel<true> : affine_rows_kernel<false>,
+                       dim3((unsigned)ceil_div(n * channels, (int64_t)256)), dim3(256), 0, (hipStream_t)stream, x, (int)n, channels,
+                       ld_x, scale, shift, relu, out, ld_out, residual, ld_res);
     EP_LAUNCH_CHECK();
     return EPRECON_OK;
-}
-
-static bool rows_vec4(const float *x, int ld_x, const float *out, int ld_out, int channels)
-{
-    return channels % 4 == 0 && ld_x % 4 == 0 && ld_out % 4 == 0 && ((uintptr_t)x | (uintptr_t)out) % 16 == 0;
 }
 
 int eprecon_affine_pool2_rows_async(const float *x, int maps, int height, int width, int channels, int ld_x, const float *scale,
                                     const float *shift, int relu, float *out, int ld_out, void *stream)
 {
-    if (!x || !out || !scale || !shift || maps <= 0 || height < 2 || width < 2 || channels <= 0 || ld_x < channels ||
-        ld_out < channels || (int64_t)maps * height * width * channels > 0x7fffffffll)
-        return EPRECON_ERR_ARG;
-    const bool v4 = rows_vec4(x, ld_x, out, ld_out, channels);
-    const int64_t total = (int64_t)maps * (height / 2) * (width / 2) * (channels / (v4 ? 4 : 1));
-    const dim3 grid((unsigned)ceil_div(total, (int64_t)256));
-    if (v4)
-        hipLaunchKernelGGL(affine_pool2_rows_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, x, maps, height, width, channels,
-                           ld_x, scale, shift, relu, out, ld_out);
-    else
-        hipLaunchKernelGGL(affine_pool2_rows_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, maps, height, width, channels,
-                           ld_x, scale, shift, relu, out, ld_out);
-    EP_LAUNCH_CHECK();
-    return EPRECON_OK;
+    return affine_join_rows(affine_pool2_rows_kernel<4>, affine_pool2_rows_kernel<1>, 2, (int64_t)maps * (height / 2) * (width / 2),
+                            x, maps, height, width, channels, ld_x, scale, shift, relu, out, ld_out, stream);
 }
 
 int eprecon_affine_up2_rows_async(const float *x, int maps, int height, int width, int channels, int ld_x, const float *scale,
                                   const float *shift, int relu, float *out, int ld_out, void *stream)
 {
-    if (!x || !out || !scale || !shift || maps <= 0 || height <= 0 || width <= 0 || channels <= 0 || ld_x < channels ||
-        ld_out < channels || (int64_t)maps * height * width * 4 * channels > 0x7fffffffll)
-        return EPRECON_ERR_ARG;
-    const bool v4 = rows_vec4(x, ld_x, out, ld_out, channels);
-    const int64_t total = (int64_t)maps * 4 * height * width * (channels / (v4 ? 4 : 1));
-    const dim3 grid((unsigned)ceil_div(total, (int64_t)256));
-    if (v4)
-        hipLaunchKernelGGL(affine_up2_rows_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, x, maps, height, width, channels,
-                           ld_x, scale, shift, relu, out, ld_out);
-    else
-        hipLaunchKernelGGL(affine_up2_rows_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, maps, height, width, channels,
-                           ld_x, scale, shift, relu, out, ld_out);
-    EP_LAUNCH_CHECK();
-    return EPRECON_OK;
+    return affine_join_rows(affine_up2_rows_kernel<4>, affine_up2_rows_kernel<1>, 1, (int64_t)maps * 4 * height * width, x, maps,
+                            height, width, channels, ld_x, scale, shift, relu, out, ld_out, stream);
 }
 
 int eprecon_batchnorm_acc_affine_async(const long long *acc, int acc_ld, int acc_c0, int channels, float eps, float *scale_out,
@@ -669,20 +633,6 @@ int eprecon_affine_rows_acc_async(const float *x, int64_t n, int channels, int l
     if (n == 0) return EPRECON_OK;
     hipLaunchKernelGGL(affine_rows_acc_kernel, dim3((unsigned)ceil_div(n * channels, (int64_t)4096)), dim3(256), 0,
                        (hipStream_t)stream, x, (int)n, channels, ld_x, acc, acc_ld, acc_c0, eps, relu, out, ld_out);
-    EP_LAUNCH_CHECK();
-    return EPRECON_OK;
-}
-
-int eprecon_affine_rows_res_async(const float *x, int64_t n, int channels, int ld_x, const float *scale,
-                                  const float *shift, const float *residual, int ld_res, int relu, float *out,
-                                  int ld_out, void *stream)
-{
-    if (!x || !out || !scale || !shift || n < 0 || channels <= 0 || ld_x < channels || ld_out < channels ||
-        (residual && ld_res < channels) || n * channels > 0x7fffffffll * 256)
-        return EPRECON_ERR_ARG;
-    if (n == 0) return EPRECON_OK;
-    hipLaunchKernelGGL(affine_rows_res_kernel, dim3((unsigned)ceil_div(n * channels, (int64_t)256)), dim3(256), 0,
-                       (hipStream_t)stream, x, (int)n, channels, ld_x, scale, shift, residual, ld_res, relu, out, ld_out);
     EP_LAUNCH_CHECK();
     return EPRECON_OK;
 }

@@ -173,14 +173,10 @@ struct Pass {
         void *ws = alloc(wsb);
         struct Done { Pass *p; void *ws; ~Done() { p->release(ws); } } done{this, ws};
         if (dry || !ok()) return;
-        if (res_aff)
-            step(eprecon_batchnorm_apply_partials_res_async(x.p, x.n, c, x.ld, partial, rows_p, rows_p, d->bn[s].gamma, d->bn[s].beta,
-                                                            d->bn[s].eps, res->p, res->ld, res_aff, res_aff + c, 1, out.p, out.ld, ws,
-                                                            wsb, stream));
-        else
-            step(eprecon_batchnorm_apply_partials_async(x.p, x.n, c, x.ld, partial, rows_p, rows_p, d->bn[s].gamma, d->bn[s].beta,
-                                                        d->bn[s].eps, res ? res->p : nullptr, res ? res->ld : 0, 1, out.p, out.ld,
-                                                        nullptr, nullptr, ws, wsb, stream));
+        step(eprecon_batchnorm_apply_partials_async(x.p, x.n, c, x.ld, partial, rows_p, rows_p, d->bn[s].gamma, d->bn[s].beta,
+                                                    d->bn[s].eps, res ? res->p : nullptr, res ? res->ld : 0, res_aff,
+                                                    res_aff ? res_aff + c : nullptr, 1, out.p, out.ld, nullptr, nullptr, ws, wsb,
+                                                    stream));
     }
     // BasicConvolutionBlock / BasicDeconvolutionBlock / the stem / a point MLP: conv -> BatchNorm -> ReLU (in place)
     Rows basic(int s, const Rows &x, const int32_t *nbr, int64_t n_out, const Rows *out_slot)

@@ -182,10 +182,6 @@ class Act:
         return self.scale, self.shift
 
 
-def _dptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def conv_bn_act(conv, bn, x, grid, out=None, aff=None, relu=True, pre_relu=False, residual=None):
     """One launch (+ a tiny finalize) for  BN( [ReLU](conv(x) + b) [+ residual] )  with x / residual given
     as Acts (their pending BatchNorms are applied on load) and the BatchNorm of the result left pending:
@@ -216,21 +212,14 @@ def conv_bn_launch(w, bias, gamma, beta, eps, k, x, grid, out=None, aff=None, re
         acc = aff if aff is not None else AccSlice.new(cout)
         assert acc.c == cout
         d.bn_acc, d.bn_acc_ld, d.bn_acc_c0 = acc.block.data_ptr(), acc.ld, acc.c0
-        d.bn_gamma, d.bn_beta = _dptr(gamma), _dptr(beta)
+        d.bn_gamma, d.bn_beta = _lib.ptr(gamma), _lib.ptr(beta)
         _lib.check(lib.eprecon_conv_desc_async(ctypes.byref(d), _lib.current_stream()), "eprecon_conv_desc_async")
         return Act(out, relu=relu, acc=acc, eps=eps)
-    if aff is None:
-        a = torch.empty((2, cout), dtype=torch.float32, device=dev)
-        aff = (a[0], a[1])
     assert not isinstance(aff, AccSlice), "an accumulator slice was handed to a launch that cannot produce into it"
     # the summaries are per workgroup: 128-row blocks (gather forms) or image tiles (tile kernel)
     partial = SP.attach_summaries(d, dev)
-    nblk, ld = partial.shape[0], d.bn_ld
     _lib.check(lib.eprecon_conv_desc_async(ctypes.byref(d), _lib.current_stream()), "eprecon_conv_desc_async")
-    _lib.check(lib.eprecon_batchnorm_finalize_affine_async(
-        partial.data_ptr(), nblk, ld, cout, _dptr(gamma), _dptr(beta), float(eps),
-        aff[0].data_ptr(), aff[1].data_ptr(), _lib.current_stream()), "eprecon_batchnorm_finalize_affine_async")
-    return Act(out, aff[0], aff[1], relu)
+    return Act(out, *SP.bn_affine(partial, gamma, beta, eps, out=aff), relu)
 
 
 def materialize(act, out=None):
@@ -249,11 +238,7 @@ def materialize(act, out=None):
             rows.data_ptr(), n, c, rows.stride(0), act.acc.block.data_ptr(), act.acc.ld, act.acc.c0, float(act.eps), int(act.relu),
             out.data_ptr(), out.stride(0), _lib.current_stream()), "eprecon_affine_rows_acc_async")
         return out
-    act.affine()
-    _lib.check(_lib.load().eprecon_affine_rows_async(
-        rows.data_ptr(), n, c, rows.stride(0), act.scale.data_ptr(), act.shift.data_ptr(), int(act.relu),
-        out.data_ptr(), out.stride(0), _lib.current_stream()), "eprecon_affine_rows_async")
-    return out
+    return SP.affine_rows(rows, *act.affine(), relu=act.relu, out=out)
 
 
 def _join_rows(name, act, grid, out, out_rows):

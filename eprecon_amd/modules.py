@@ -256,12 +256,6 @@ class TrainBatchNorm1d(nn.BatchNorm1d):
 # channels-last activations runs on the HIP BatchNorm kernels: a [N,C,H,W] channels-last tensor IS a
 # row-major [N*H*W, C] matrix, and MIOpen's spatial BN costs ~26 us per call on these small maps)
 # ------------------------------------------------------------------------------------------------
-def _rows(x):
-    """channels-last [N,C,H,W] -> its [N*H*W, C] row-major view (no copy)"""
-    n, c, h, w = x.shape
-    return x.permute(0, 2, 3, 1).reshape(n * h * w, c)
-
-
 def _hip_bn_ok(x):
     return (x.is_cuda and not torch.is_grad_enabled() and x.dim() == 4 and x.shape[1] <= 256
             and x.is_contiguous(memory_format=torch.channels_last) and x.dtype == torch.float32)
@@ -271,7 +265,7 @@ def bn2d_train(bn, x, relu=False):
     """train-mode BatchNorm2d (+ReLU): HIP kernels for channels-last CUDA tensors under no_grad,
     else the PyTorch module"""
     if _hip_bn_ok(x):
-        rows = _rows(x)
+        rows = D2.rows_of(x)
         SP.batchnorm_train(rows, bn.weight, bn.bias, bn.eps, relu=relu, out=rows)
         return x
     y = bn(x)

@@ -64,6 +64,16 @@ def _ld(t):
     return ld
 
 
+def _res(residual):
+    """(pointer, row stride) of an optional residual operand"""
+    return _lib.ptr(residual), 0 if residual is None else _ld(residual)
+
+
+def _rows_out(x, out):
+    """`out`, or new float32 rows of x's shape"""
+    return torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device) if out is None else out
+
+
 class HashGrid:
     """device hash table over a coordinate set (eprecon_hash_*)"""
 
@@ -637,14 +647,11 @@ def sparse_conv_ln(x, weight, nbr, bias, ln_weight, ln_bias, ln_eps, out=None, r
 
 def affine_rows(x, scale, shift, residual=None, relu=False, out=None):
     """out = [relu]( x * scale + shift [+ residual] ): a BatchNorm whose statistics its producer finished; out may be x"""
-    lib = _lib.load()
     n, c = x.shape
-    if out is None:
-        out = torch.empty((n, c), dtype=torch.float32, device=x.device)
-    _lib.check(lib.eprecon_affine_rows_res_async(
-        _lib.ptr(x), n, c, _ld(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual),
-        _ld(residual) if residual is not None else 0, int(relu), _lib.ptr(out), _ld(out), _lib.current_stream()),
-        "eprecon_affine_rows_res_async")
+    out = _rows_out(x, out)
+    _lib.check(_lib.load().eprecon_affine_rows_async(
+        _lib.ptr(x), n, c, _ld(x), _lib.ptr(scale), _lib.ptr(shift), *_res(residual), int(relu), _lib.ptr(out), _ld(out),
+        _lib.current_stream()), "eprecon_affine_rows_async")
     return out
 
 
@@ -656,16 +663,16 @@ def conv_stats(x, weight, nbr=None, in_affine=None, out=None, bias=None):
     return conv_call(x, weight, nbr, bias, out, in_affine=in_affine, stats=True, launch=rows > 0)[:2]
 
 
-def bn_affine(partial, gamma, beta, eps):
-    """summaries -> the BatchNorm in affine form (scale, shift), to be applied by a consumer on load"""
-    lib = _lib.load()
+def bn_affine(partial, gamma, beta, eps, out=None):
+    """summaries -> the BatchNorm in affine form (scale, shift), to be applied by a consumer on load; out: the (scale, shift)
+    slices to fill"""
     c = partial.shape[2]
     nblk, ld = summary_layout(partial)
-    aff = torch.empty((2, c), dtype=torch.float32, device=partial.device)
-    _lib.check(lib.eprecon_batchnorm_finalize_affine_async(
-        partial.data_ptr(), nblk, ld, c, _lib.ptr(gamma), _lib.ptr(beta), float(eps), aff[0].data_ptr(),
-        aff[1].data_ptr(), _lib.current_stream()), "eprecon_batchnorm_finalize_affine_async")
-    return aff[0], aff[1]
+    scale, shift = torch.empty((2, c), dtype=torch.float32, device=partial.device) if out is None else out
+    _lib.check(_lib.load().eprecon_batchnorm_finalize_affine_async(
+        partial.data_ptr(), nblk, ld, c, _lib.ptr(gamma), _lib.ptr(beta), float(eps), scale.data_ptr(), shift.data_ptr(),
+        _lib.current_stream()), "eprecon_batchnorm_finalize_affine_async")
+    return scale, shift
 
 
 def batchnorm_apply_partials(x, partial, gamma=None, beta=None, eps=1e-5, residual=None, relu=False, out=None,
@@ -676,22 +683,15 @@ def batchnorm_apply_partials(x, partial, gamma=None, beta=None, eps=1e-5, residu
     n, c = x.shape
     assert partial.shape[1:] == (3, c)
     nblk, ld = summary_layout(partial)
-    if out is None:
-        out = torch.empty((n, c), dtype=torch.float32, device=x.device)
+    out = _rows_out(x, out)
     # mean / var scratch is a per-call buffer (not the shared grow-only workspace): independent branches
     # of the 2D stack run concurrently on several streams
     ws = torch.empty((lib.eprecon_batchnorm_apply_workspace_bytes(c),), dtype=torch.uint8, device=x.device)
-    if res_affine is not None:
-        _lib.check(lib.eprecon_batchnorm_apply_partials_res_async(
-            _lib.ptr(x), n, c, _ld(x), _lib.ptr(partial), nblk, ld, _lib.ptr(gamma), _lib.ptr(beta), float(eps),
-            _lib.ptr(residual), _ld(residual), _lib.ptr(res_affine[0]), _lib.ptr(res_affine[1]), int(relu), _lib.ptr(out),
-            _ld(out), _lib.ptr(ws), ws.numel(), _lib.current_stream()), "eprecon_batchnorm_apply_partials_res_async")
-        return out
+    res_scale, res_shift = (None, None) if res_affine is None else res_affine[:2]
     _lib.check(lib.eprecon_batchnorm_apply_partials_async(
-        _lib.ptr(x), n, c, _ld(x), _lib.ptr(partial), nblk, ld, _lib.ptr(gamma), _lib.ptr(beta),
-        float(eps), _lib.ptr(residual), _ld(residual) if residual is not None else 0, int(relu), _lib.ptr(out),
-        _ld(out), None, None, _lib.ptr(ws), ws.numel(), _lib.current_stream()),
-        "eprecon_batchnorm_apply_partials_async")
+        _lib.ptr(x), n, c, _ld(x), _lib.ptr(partial), nblk, ld, _lib.ptr(gamma), _lib.ptr(beta), float(eps), *_res(residual),
+        _lib.ptr(res_scale), _lib.ptr(res_shift), int(relu), _lib.ptr(out), _ld(out), None, None, _lib.ptr(ws), ws.numel(),
+        _lib.current_stream()), "eprecon_batchnorm_apply_partials_async")
     return out
 
 
@@ -699,27 +699,22 @@ def batchnorm_train(x, gamma=None, beta=None, eps=1e-5, residual=None, relu=Fals
     """train-mode BatchNorm over all rows (+ optional residual add and ReLU); out may be x"""
     lib = _lib.load()
     n, c = x.shape
-    if out is None:
-        out = torch.empty((n, c), dtype=torch.float32, device=x.device)
+    out = _rows_out(x, out)
     ws = _lib.workspace(lib.eprecon_batchnorm_workspace_bytes(n, c), x.device)
     _lib.check(lib.eprecon_batchnorm_train_async(
-        _lib.ptr(x), n, c, _ld(x), _lib.ptr(gamma), _lib.ptr(beta), float(eps), _lib.ptr(residual),
-        _ld(residual) if residual is not None else 0, int(relu), _lib.ptr(out), _ld(out), None, None,
-        _lib.ptr(ws), ws.numel(), _lib.current_stream()), "eprecon_batchnorm_train_async")
+        _lib.ptr(x), n, c, _ld(x), _lib.ptr(gamma), _lib.ptr(beta), float(eps), *_res(residual), int(relu), _lib.ptr(out),
+        _ld(out), None, None, _lib.ptr(ws), ws.numel(), _lib.current_stream()), "eprecon_batchnorm_train_async")
     return out
 
 
 def rowwise_layernorm(x, gamma=None, beta=None, eps=1e-5, residual=None, pre_relu=False, post_relu=False,
                       out=None):
     """y = [relu]( LN( [relu](x) [+ residual] ) * gamma + beta ) per row; out may be x"""
-    lib = _lib.load()
     n, c = x.shape
-    if out is None:
-        out = torch.empty((n, c), dtype=torch.float32, device=x.device)
-    _lib.check(lib.eprecon_rowwise_layernorm_async(
-        _lib.ptr(x), n, c, _ld(x), _lib.ptr(residual), _ld(residual) if residual is not None else 0,
-        _lib.ptr(gamma), _lib.ptr(beta), float(eps), int(pre_relu), int(post_relu), _lib.ptr(out),
-        _ld(out), _lib.current_stream()), "eprecon_rowwise_layernorm_async")
+    out = _rows_out(x, out)
+    _lib.check(_lib.load().eprecon_rowwise_layernorm_async(
+        _lib.ptr(x), n, c, _ld(x), *_res(residual), _lib.ptr(gamma), _lib.ptr(beta), float(eps), int(pre_relu), int(post_relu),
+        _lib.ptr(out), _ld(out), _lib.current_stream()), "eprecon_rowwise_layernorm_async")
     return out
 
 

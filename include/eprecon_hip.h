@@ -38,7 +38,8 @@ extern "C" {
 #define EPRECON_ERR_UNSUPPORTED (-3)
 #define EPRECON_ERR_HIP_BASE (-1000)
 
-#define EPRECON_ABI_VERSION 1
+/* goes up when an exported function keeps its name with another argument list: the loader refuses a library of another version */
+#define EPRECON_ABI_VERSION 2
 int eprecon_abi_version(void);
 /* name of the gfx target the kernels were compiled for, e.g. "gfx950" */
 const char *eprecon_build_arch(void);
@@ -429,9 +430,11 @@ int eprecon_conv_dense3d_kind(const eprecon_conv_desc *desc);
 int eprecon_batchnorm_finalize_affine_async(const float *partial, int64_t nblk, int64_t ld, int channels, const float *gamma,
                                             const float *beta, float eps, float *scale_out, float *shift_out,
                                             void *stream);
-/* out[i, c] = [relu]( x[i, c] * scale[c] + shift[c] ); out may alias x */
+/* out[i, c] = [relu]( x[i, c] * scale[c] + shift[c] [+ residual[i, c]] ): a producer-finished BatchNorm materialised, and the
+ * tail of the residual blocks (models/modules.py:46-72); residual may be NULL (else ld_res >= channels); out may alias x */
 int eprecon_affine_rows_async(const float *x, int64_t n, int channels, int ld_x, const float *scale,
-                              const float *shift, int relu, float *out, int ld_out, void *stream);
+                              const float *shift, const float *residual, int ld_res, int relu, float *out,
+                              int ld_out, void *stream);
 /*
  * The joins of the 2D fusion stack in one launch each.  x: the pixel rows f32[maps*height*width, channels] (row stride ld_x)
  * of a level with its pending BatchNorm (scale, shift, relu), applied on load as eprecon_affine_rows_async does.
@@ -444,11 +447,6 @@ int eprecon_affine_pool2_rows_async(const float *x, int maps, int height, int wi
                                     const float *shift, int relu, float *out, int ld_out, void *stream);
 int eprecon_affine_up2_rows_async(const float *x, int maps, int height, int width, int channels, int ld_x, const float *scale,
                                   const float *shift, int relu, float *out, int ld_out, void *stream);
-/* out[i, c] = [relu]( x[i, c] * scale[c] + shift[c] + residual[i, c] ): the tail of the residual blocks
- * (models/modules.py:46-72) from a producer-finished BatchNorm; residual may be NULL; out may alias x */
-int eprecon_affine_rows_res_async(const float *x, int64_t n, int channels, int ld_x, const float *scale,
-                                  const float *shift, const float *residual, int ld_res, int relu, float *out,
-                                  int ld_out, void *stream);
 /*
  * Kernel map of a dense 2D 'same' convolution (odd ksize) over `maps` images of height x width
  * pixels stored as rows [maps][height][width] of a channels-last tensor:
@@ -498,21 +496,16 @@ int eprecon_batchnorm_train_async(const float *x, int64_t n, int channels, int l
                                   int relu, float *out, int ld_out, float *mean_out, float *var_out,
                                   void *workspace, size_t workspace_bytes, void *stream);
 /* second half of the same BatchNorm from producer-side summaries partial f32[3][channels][ld], ld >= nblk
- * (count, mean, M2 per block, channel-major as eprecon_batchnorm_finalize_affine_async reads them, merged in block order) */
+ * (count, mean, M2 per block, channel-major as eprecon_batchnorm_finalize_affine_async reads them, merged in block order).
+ * res_scale / res_shift (both or neither, and only with a residual, else EPRECON_ERR_ARG): the residual carries a pending
+ * BatchNorm of its own in affine form (the 1x1 skip convolution + BatchNorm of a residual block, models/modules.py:57-65,71):
+ * residual' = residual * res_scale + res_shift on load.  mean_out / var_out optional f32[channels]. */
 size_t eprecon_batchnorm_apply_workspace_bytes(int channels);
-int eprecon_batchnorm_apply_partials_async(const float *x, int64_t n, int channels, int ld_x,
-                                           const float *partial, int64_t nblk, int64_t ld, const float *gamma,
-                                           const float *beta, float eps, const float *residual,
-                                           int ld_res, int relu, float *out, int ld_out, float *mean_out,
-                                           float *var_out, void *workspace, size_t workspace_bytes,
-                                           void *stream);
-/* the same with a residual operand that carries a pending BatchNorm of its own in affine form (the 1x1 skip convolution +
- * BatchNorm of a residual block, models/modules.py:57-65,71): residual' = residual * res_scale + res_shift on load */
-int eprecon_batchnorm_apply_partials_res_async(const float *x, int64_t n, int channels, int ld_x, const float *partial,
-                                               int64_t nblk, int64_t ld, const float *gamma, const float *beta, float eps,
-                                               const float *residual, int ld_res, const float *res_scale,
-                                               const float *res_shift, int relu, float *out, int ld_out, void *workspace,
-                                               size_t workspace_bytes, void *stream);
+int eprecon_batchnorm_apply_partials_async(const float *x, int64_t n, int channels, int ld_x, const float *partial,
+                                           int64_t nblk, int64_t ld, const float *gamma, const float *beta, float eps,
+                                           const float *residual, int ld_res, const float *res_scale,
+                                           const float *res_shift, int relu, float *out, int ld_out, float *mean_out,
+                                           float *var_out, void *workspace, size_t workspace_bytes, void *stream);
 /* per row: t = x; if pre_relu t = relu(t); if residual t += residual; y = LN(t) * gamma + beta;
  * if post_relu y = relu(y).  out may alias x. */
 int eprecon_rowwise_layernorm_async(const float *x, int64_t n, int channels, int ld_x,

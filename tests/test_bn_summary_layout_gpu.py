@@ -28,7 +28,7 @@ def _summaries(nblk, c, seed):
 
 
 def _merge(a, b):
-    """chan_merge (csrc/norm.hip) element-wise in float32, the same operations in the same order"""
+    """chan_merge (csrc/conv_common.hpp) element-wise in float32, the same operations in the same order"""
     na, ma, qa = a
     nb, mb, qb = b
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -133,7 +133,7 @@ def test_finalize_statistics_is_the_documented_merge_order(nblk):
         var = torch.empty(c, dtype=torch.float32, device=_dev())
         ws = torch.empty((lib.eprecon_batchnorm_apply_workspace_bytes(c),), dtype=torch.uint8, device=_dev())
         _lib.check(lib.eprecon_batchnorm_apply_partials_async(
-            x.data_ptr(), 1, c, c, p.data_ptr(), nblk, p.stride(2), None, None, ctypes.c_float(EPS), None, 0, 0,
+            x.data_ptr(), 1, c, c, p.data_ptr(), nblk, p.stride(2), None, None, ctypes.c_float(EPS), None, 0, None, None, 0,
             out.data_ptr(), c, mean.data_ptr(), var.data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream()),
             "eprecon_batchnorm_apply_partials_async")
         assert np.array_equal(mean.cpu().numpy().view(np.uint32), want_mean.view(np.uint32)), (nblk, c)

@@ -37,7 +37,7 @@ def test_ctypes_table_matches_header():
 
 
 def test_build_identity(lib):
-    assert lib.eprecon_abi_version() == 1
+    assert lib.eprecon_abi_version() == 2
     assert lib.eprecon_build_arch() == b"gfx950"
 
 

@@ -163,7 +163,7 @@ def _summaries(x, rows_per_block):
 
 @pytest.mark.parametrize("n,c,rpb", [(4000, 24, 37), (20011, 48, 64), (777, 256, 5)])
 def test_bn_apply_partials_residual_affine(dev, n, c, rpb):
-    """eprecon_batchnorm_apply_partials_res_async: a residual with its own pitch and its own pending BatchNorm"""
+    """eprecon_batchnorm_apply_partials_async with res_scale / res_shift: a residual with its own pitch and its own pending BatchNorm"""
     from eprecon_amd import sparse as SP
     x = data(n, c, dev, "offset" if c == 48 else "normal", seed=n)
     part = _summaries(x, rpb)
@@ -203,12 +203,90 @@ def test_bn_affine_and_affine_rows(dev, n, c):
     out2 = Out(n, c, dev, c + 3, 3)
 
     def raw():
-        _lib.check(_lib.load().eprecon_affine_rows_async(x.data_ptr(), n, c, c, sc.data_ptr(), sh.data_ptr(), 0, out2.t.data_ptr(),
-                                                         out2.buf.stride(0), _lib.current_stream()), "eprecon_affine_rows_async")
+        _lib.check(_lib.load().eprecon_affine_rows_async(x.data_ptr(), n, c, c, sc.data_ptr(), sh.data_ptr(), None, 0, 0,
+                                                         out2.t.data_ptr(), out2.buf.stride(0), _lib.current_stream()), "eprecon_affine_rows_async")
         return out2.t.clone()
     y2 = twice(raw)
     out2.untouched()
     within(f"affine_rows n={n} C={c}", y2, (yb, eb))
+
+
+@pytest.mark.parametrize("residual", (False, True))
+@pytest.mark.parametrize("n,c,pitch", [(1, 1, 1), (5, 3, 7), (86, 3, 3), (257, 24, 40)])
+def test_affine_rows_one_entry(dev, n, c, pitch, residual):
+    """the one affine-rows kernel with and without a residual (its own pitch), n * c on both sides of a 256-thread workgroup:
+    one rounding of the fma (norm_ref's GEMV rule with K = 1), one of the add; the same bits when `out` is `x`"""
+    from eprecon_amd import sparse as SP
+    g = torch.Generator(device="cpu").manual_seed(n + c)
+    x0 = data(n, c, dev, seed=n)
+    sc, sh = torch.randn(c, generator=g).to(dev), torch.randn(c, generator=g).to(dev)
+    res = torch.randn(n, c + 2, generator=g).to(dev)[:, 1:1 + c] if residual else None
+    xin = Out(n, c, dev, pitch, pitch - c)
+    out = Out(n, c, dev, pitch + 3, 2)
+    xin.t.copy_(x0)
+    y = twice(lambda: SP.affine_rows(xin.t, sc, sh, residual=res, relu=True, out=out.t).clone())
+    out.untouched()
+    yr = R.f64(x0) * R.f64(sc) + R.f64(sh)
+    er = R.gam(1) * ((R.f64(x0) * R.f64(sc)).abs() + R.f64(sh).abs())
+    if residual:
+        yr, er = R.add(yr, er, R.f64(res), torch.zeros_like(er))
+    within(f"affine_rows n={n} C={c} pitch={pitch} res={residual}", y, (yr.clamp_min(0.0), er))
+    assert SP.affine_rows(xin.t, sc, sh, residual=res, relu=True, out=xin.t) is xin.t
+    xin.untouched()
+    assert torch.equal(xin.t.contiguous().view(torch.int32), y.view(torch.int32)), "out aliasing x changes the bits"
+
+
+@pytest.mark.parametrize("nblk", (1, 257))
+@pytest.mark.parametrize("c", (4, 5))
+def test_bn_apply_partials_one_entry(dev, c, nblk):
+    """the one apply-partials entry on both sides of the one-launch limit (C <= 4) and with one and two summary rows per thread:
+    no residual, a plain residual, a residual with its pending BatchNorm, and mean_out / var_out given -- then the same rows,
+    and the statistics in the bits of the documented merge order of the same summaries"""
+    import ctypes
+
+    import test_bn_summary_layout_gpu as LAYOUT
+    from eprecon_amd import sparse as SP
+    _lib = lib()
+    rpb = 3
+    n = nblk * rpb - 1
+    x = data(n, c, dev, seed=nblk + c)
+    part = _summaries(x, rpb)
+    assert part.shape[0] == nblk
+    g = torch.Generator(device="cpu").manual_seed(c)
+    gamma, beta = torch.randn(c, generator=g).to(dev), torch.randn(c, generator=g).to(dev)
+    rs, rsh = torch.randn(c, generator=g).to(dev), torch.randn(c, generator=g).to(dev)
+    res = torch.randn(n, c + 3, generator=g).to(dev)[:, 2:2 + c]
+    yb, eb = R.bn_train(x, gamma, beta, 1e-5, R.m_bn_train(n, c, nblk) + 4)   # (+ the rounding of the stored summaries)
+    rv = R.f64(res) * R.f64(rs) + R.f64(rsh)
+    plain = None
+    for name, kw, ref in (("none", {}, (yb, eb)),
+                          ("res", {"residual": res}, R.add(yb, eb, R.f64(res), torch.zeros_like(eb))),
+                          ("res_affine", {"residual": res, "res_affine": (rs, rsh)}, R.add(yb, eb, rv, R.U * rv.abs()))):
+        out = Out(n, c, dev, c + 5, 1)
+        y = twice(lambda: SP.batchnorm_apply_partials(x, part, gamma, beta, 1e-5, relu=True, out=out.t, **kw).clone())
+        out.untouched()
+        within(f"bn_apply_partials {name} C={c} nblk={nblk}", y, (ref[0].clamp_min(0.0), ref[1]))
+        plain = y if plain is None else plain
+    out = Out(n, c, dev, c + 5, 1)
+    stats = torch.full((2, c + GUARD), NAN, device=dev)
+    L = _lib.load()
+    ws = torch.empty((L.eprecon_batchnorm_apply_workspace_bytes(c),), dtype=torch.uint8, device=dev)
+    nb, ld = SP.summary_layout(part)
+
+    def raw():
+        _lib.check(L.eprecon_batchnorm_apply_partials_async(
+            x.data_ptr(), n, c, c, part.data_ptr(), nb, ld, gamma.data_ptr(), beta.data_ptr(), ctypes.c_float(1e-5), None, 0, None,
+            None, 1, out.t.data_ptr(), out.buf.stride(0), stats[0].data_ptr(), stats[1].data_ptr(), ws.data_ptr(), ws.numel(),
+            _lib.current_stream()), "eprecon_batchnorm_apply_partials_async")
+        return out.t.clone(), stats.clone()
+    y, st = twice(raw)
+    out.untouched()
+    assert torch.equal(y.view(torch.int32), plain.view(torch.int32)), "asking for the statistics changes the rows"
+    assert bool(st[:, c:].isnan().all()), "statistics past C written"
+    want_mean, want_var = LAYOUT._stats_reference(part.cpu().numpy())
+    got = st[:, :c].cpu().numpy()
+    assert (got[0].view("uint32") == want_mean.view("uint32")).all(), (got[0], want_mean)
+    assert (got[1].view("uint32") == want_var.view("uint32")).all(), (got[1], want_var)
 
 
 # ---- row-wise LayerNorm ------------------------------------------------------------------------------------------------
@@ -493,6 +571,20 @@ def test_refusals(dev):
     acc = torch.zeros(2 * 1024, dtype=torch.int64, device=dev)
     out = torch.full((64, 520), NAN, device=dev)
     rc = L.eprecon_affine_rows_acc_async(x.data_ptr(), 64, 513, 520, acc.data_ptr(), 1024, 0, 1e-5, 0, out.data_ptr(), 520, st)
+    assert rc == -1, rc
+    # the one apply-partials entry: res_scale without res_shift, res_scale / res_shift without a residual, a residual pitch
+    # below C (the one affine-rows entry as well)
+    import ctypes
+    c = 8
+    part = torch.ones((3, c, 4), device=dev)
+    v = torch.ones(c, device=dev)
+    aws = torch.empty((L.eprecon_batchnorm_apply_workspace_bytes(c),), dtype=torch.uint8, device=dev)
+    for res, ld_res, rs, rsh in ((x, 520, v, None), (x, 520, None, v), (None, 0, v, v), (x, c - 1, None, None), (x, c - 1, v, v)):
+        rc = L.eprecon_batchnorm_apply_partials_async(
+            x.data_ptr(), 64, c, 520, part.data_ptr(), 4, 4, None, None, ctypes.c_float(1e-5), _lib.ptr(res), ld_res, _lib.ptr(rs),
+            _lib.ptr(rsh), 0, out.data_ptr(), 520, None, None, aws.data_ptr(), aws.numel(), st)
+        assert rc == -1, (ld_res, rs is None, rsh is None, rc)
+    rc = L.eprecon_affine_rows_async(x.data_ptr(), 64, c, 520, v.data_ptr(), v.data_ptr(), x.data_ptr(), c - 1, 0, out.data_ptr(), 520, st)
     assert rc == -1, rc
     torch.cuda.synchronize()
     assert bool(aff.isnan().all()) and bool(out.isnan().all())
