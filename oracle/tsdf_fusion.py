@@ -80,7 +80,7 @@ def integrate(tsdf, weight, origin, voxel_size, depth, intr, pose_or_w2c, trunc,
     diff = (d - cz_).astype(F32)
     valid &= (d > 0) if variant == "torch" else (d != 0)
     valid &= ~(diff < -F32(trunc))
-    dist = np.minimum(F32(1.0), (diff / F32(trunc)).astype(F32))
+    dist = np.fmin(F32(1.0), (diff / F32(trunc)).astype(F32))       # fminf: a NaN depth ("cuda" lets it through) gives 1
     tv, wv = tsdf.reshape(-1), weight.reshape(-1)
     w_old = wv[valid]
     w_new = (w_old + F32(obs_weight)).astype(F32)
