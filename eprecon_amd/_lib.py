@@ -23,6 +23,11 @@ _vp, _i, _i64, _f, _sz = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_siz
 SIGNATURES = {
     "eprecon_abi_version": (_i, []),
     "eprecon_build_arch": (_c.c_char_p, []),
+    "eprecon_count_mailbox": (_i, []),
+    "eprecon_mailbox_acquire": (_i, [_i, _vp]),
+    "eprecon_mailbox_wait": (_i, [_vp, _i64, _vp]),
+    "eprecon_mailbox_release": (_i, [_vp]),
+    "eprecon_mailbox_free_slots": (_i, []),
     "eprecon_back_project_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i, _i, _i]),
     "eprecon_back_project_async": (_i, [_vp, _i64, _vp, _i, _f, _vp, _i, _vp, _i, _i, _i, _i, _i, _i,
                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -82,6 +87,8 @@ SIGNATURES = {
     "eprecon_init_select_workspace_bytes": (_sz, [_i, _i]),
     "eprecon_init_select_async": (_i, [_vp, _vp, _i64, _f, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "eprecon_init_select_dense_async": (_i, [_vp, _vp, _i64, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "eprecon_init_select_mb_async": (_i, [_vp, _vp, _i64, _f, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "eprecon_init_select_dense_mb_async": (_i, [_vp, _vp, _i64, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
     "eprecon_upsample_async": (_i, [_vp, _i, _vp, _i64, _i, _i, _vp, _vp, _vp]),
     "eprecon_aligned_coords_async": (_i, [_vp, _i64, _vp, _i, _f, _vp, _vp, _vp]),
     "eprecon_point_quantize_async": (_i, [_vp, _i64, _f, _vp, _vp, _vp]),
@@ -219,6 +226,9 @@ SIGNATURES = {
 VIEWS_TILE_H, VIEWS_MAX_KSIZE = 16, 9
 
 EPRECON_OK, EPRECON_EMPTY = 0, 1
+EPRECON_ERR_TIMEOUT = -4
+MAILBOX_WORDS = 15               # include/eprecon_hip.h: EPRECON_MAILBOX_WORDS
+MAILBOX_WAIT_US = 2_000_000      # the cap of every host wait on a count mailbox: a safety condition far above any step
 ABI_VERSION = 2
 
 
@@ -313,7 +323,13 @@ class BpCall(ctypes.Structure):
                 ("n_valid_dev", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
                 ("phase", ctypes.c_int32), ("out_feats", ctypes.c_void_p), ("out_mean", ctypes.c_void_p),
                 ("out_coords", ctypes.c_void_p), ("out_grid", ctypes.c_void_p), ("out_mask", ctypes.c_void_p),
-                ("rank", ctypes.c_void_p)]
+                ("rank", ctypes.c_void_p), ("counts_host", ctypes.c_void_p), ("counts_seq", ctypes.c_uint32)]
+
+
+class MailboxSlot(ctypes.Structure):
+    """include/eprecon_hip.h: eprecon_mailbox_slot"""
+    _fields_ = [("payload_dev", ctypes.c_void_p), ("payload_host", ctypes.c_void_p), ("seq", ctypes.c_uint32),
+                ("index", ctypes.c_int32), ("words", ctypes.c_int32), ("armed", ctypes.c_int32)]
 
 
 class AdamSegment(ctypes.Structure):
@@ -581,6 +597,87 @@ class PinnedRead:
             requeue_deferred(self._pending)
         except Exception:  # noqa: BLE001  (interpreter shutdown)
             pass
+
+
+def has_deferred(stream="current"):
+    """are checks pending on `stream` (as take_deferred names it)?  Nothing is removed."""
+    st = current_stream() if stream == "current" else stream
+    with _DEFERRED_LOCK:
+        return any(stream is None or it[3] == st for it in _DEFERRED)
+
+
+class MailboxRead:
+    """PinnedRead without the copy: the counts arrive through a slot of the library's count mailbox (include/eprecon_hip.h),
+    stored there by the kernel thread that writes them to device memory, so nothing is queued on the stream — no copy launch,
+    no event.  Made BEFORE the launch that publishes (mailbox_read(words)), because that launch is handed `.payload_dev` and
+    `.seq` (or `.slot`); queued(counts) then arms it.  result() waits on the host, at most MAILBOX_WAIT_US, for the slot's
+    sequence word; on a timeout or any mailbox error it synchronises the stream and reads `counts` from the device instead,
+    and raises nothing.  It is still a blocking host read and is counted as one.  Deferred checks do not ride on a mailbox
+    read: mailbox_read() hands out none while checks are pending on the stream, so the caller's PinnedRead takes them."""
+
+    def __init__(self, words):
+        self.slot = MailboxSlot()
+        self._held = load().eprecon_mailbox_acquire(int(words), ctypes.byref(self.slot)) == EPRECON_OK
+        self._counts = self._stream = self._host = self.from_mailbox = None
+
+    ok = property(lambda self: self._held)
+    payload_dev = property(lambda self: self.slot.payload_dev)
+    seq = property(lambda self: self.slot.seq)
+
+    def queued(self, counts):
+        """a launch that publishes into the slot is on the current stream; counts: the device words it also writes (the slot's
+        `words` first elements are what result() returns when the mailbox fails)"""
+        self.slot.armed = 1
+        self._counts, self._stream = counts, current_stream()
+        return self
+
+    def release(self):
+        if self._held:
+            self._held = False
+            load().eprecon_mailbox_release(ctypes.byref(self.slot))
+
+    def result(self, timeout_us=MAILBOX_WAIT_US):
+        count_host_read()
+        return self.wait(timeout_us)
+
+    def wait(self, timeout_us=MAILBOX_WAIT_US):
+        """result() for a caller that counts several slots as the one host read they are (back_project.PendingLevels)"""
+        if self._host is None:
+            if self._counts is None:
+                raise EpreconError("MailboxRead.result() before queued(): no launch publishes into the slot")
+            out = (ctypes.c_int32 * self.slot.words)()
+            rc = load().eprecon_mailbox_wait(ctypes.byref(self.slot), int(timeout_us), out) if self._held else EPRECON_ERR_TIMEOUT
+            self.from_mailbox = rc == EPRECON_OK        # (False: the counts below came from the device after all)
+            if rc == EPRECON_OK:
+                self._host = list(out)
+            else:       # the copy path after all: everything queued on the publisher's stream, then the device words
+                st = torch.cuda.ExternalStream(self._stream) if self._stream else torch.cuda.default_stream()
+                st.synchronize()
+                self._host = self._counts.reshape(-1)[:self.slot.words].tolist()
+            self.release()
+        return self._host
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:  # noqa: BLE001  (interpreter shutdown)
+            pass
+
+
+_MAILBOX_ON = None
+
+
+def mailbox_read(words):
+    """-> a MailboxRead holding a slot of `words` int32, or None: the caller takes the copy path (PinnedRead) — the switch is
+    off (EPRECON_COUNT_MAILBOX=0), more words than a slot holds, every slot handed out, or deferred checks are pending on the
+    current stream (they ride with copy reads, and are not to be stranded)"""
+    global _MAILBOX_ON
+    if _MAILBOX_ON is None:
+        _MAILBOX_ON = bool(load().eprecon_count_mailbox())
+    if not _MAILBOX_ON or not 0 < words <= MAILBOX_WORDS or has_deferred():
+        return None
+    read = MailboxRead(words)
+    return read if read.ok else None
 
 
 def drain_deferred():

@@ -132,9 +132,12 @@ class PendingBackProject:
 class CountedBackProject:
     """the count half of a back-projection (count_async), to be handed to run_async(counted=...) with the maps"""
 
-    def __init__(self, shape, inputs, call, count, n_valid_dev, ws, stream):
+    def __init__(self, shape, inputs, call, count, n_valid_dev, ws, stream, mailbox=None, early=False):
         self.shape, self.inputs, self.call, self.count = shape, inputs, call, count      # call: the _lib.BpCall that was queued
         self.n_valid_dev, self.ws, self.stream = n_valid_dev, ws, stream
+        # mailbox: the _lib.MailboxRead whose slot `call` carries, or None (the counts are copied); early: the count half has
+        # published into it already (count_async), so the gather half is handed none
+        self.mailbox, self.early = mailbox, early
 
 
 def count_async(coords, origin, voxel_size, feats_shape, krcam, min_view, mode=MODE_MEAN, stream=None):
@@ -153,16 +156,24 @@ def count_async(coords, origin, voxel_size, feats_shape, krcam, min_view, mode=M
     ws = torch.empty((lib.eprecon_back_project_workspace_bytes(n, b, v, c, h, w, LAYOUT_NHWC),), dtype=torch.uint8, device=dev)
 
     call = _call(inputs, None, shape, LAYOUT_NHWC, voxel_size, min_view, mode, {"count": count}, n_valid_dev, ws, phase=1)
+    # The counts are final once the count has run.  With a count mailbox the count half publishes them itself (one more
+    # one-workgroup launch, on `stream`), and the host has them long before the gather half is even queued.
+    mb = _lib.mailbox_read(1 + b) if n > 0 else None
+    if mb is not None:
+        call.counts_host, call.counts_seq = mb.payload_dev, mb.seq
 
     def queue():
         _lib.check(lib.eprecon_back_project_call_async(ctypes.byref(call), _lib.current_stream()), "eprecon_back_project_call_async")
+        if mb is not None:
+            mb.queued(n_valid_dev)
     if stream is None:
         queue()
     else:
         stream.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(stream):
             queue()
-    return CountedBackProject(shape, inputs + (float(voxel_size), int(min_view), mode), call, count, n_valid_dev, ws, stream)
+    return CountedBackProject(shape, inputs + (float(voxel_size), int(min_view), mode), call, count, n_valid_dev, ws, stream,
+                              mailbox=mb, early=mb is not None)
 
 
 class PreparedMaps:
@@ -175,18 +186,25 @@ class PreparedMaps:
 
 class PendingLevels:
     """The gather halves of prepare_levels_async's levels — run_async(..., hd.nhwc, ..., hold_read=True, counted=hd) for every
-    handle hd — behind ONE pinned read of the tensor their counts are slices of (queued here: behind the last gather on the
-    current stream; the deferred checks pending there ride along).  results() -> what every PendingBackProject.result() would
+    handle hd — behind ONE read of their counts: a count mailbox slot per level when the handles carry them (nothing is
+    queued), else one pinned read of the tensor the counts are slices of (queued here: behind the last gather on the current
+    stream; the deferred checks pending there ride along).  results() -> what every PendingBackProject.result() would
     have returned, one blocking read in all."""
 
     def __init__(self, pends, handles):
         self._pends, self._offsets, self._host = list(pends), [hd.n_valid_off for hd in handles], None
         assert len(self._pends) == len(self._offsets) and all(hd.n_valid_all is handles[0].n_valid_all for hd in handles)
         assert all(p.n_valid_dev.data_ptr() == hd.n_valid_dev.data_ptr() for p, hd in zip(self._pends, handles))
-        self._read = _lib.PinnedRead(handles[0].n_valid_all)
+        self._slots = [hd.mailbox for hd in handles]        # (prepare_levels_async: every level has one, or none has)
+        self._read = None if all(m is not None for m in self._slots) else _lib.PinnedRead(handles[0].n_valid_all)
 
     def results(self):
-        if self._host is None:
+        if self._host is None and self._read is None:
+            _lib.count_host_read()
+            self._host = [None] * (self._offsets[-1] + 1 + self._pends[-1]._batch)
+            for m, p, o in zip(self._slots, self._pends, self._offsets):
+                self._host[o:o + 1 + p._batch] = m.wait()
+        elif self._host is None:
             self._host = self._read.result()
         return [p.result_from(self._host[o:o + 1 + p._batch]) for p, o in zip(self._pends, self._offsets)]
 
@@ -214,6 +232,11 @@ def prepare_levels_async(levels, stream=None):
         rows.append((shape, feats_c, layout, inputs, float(voxel_size), int(min_view), mode))
     n_valid_all = torch.empty((sum(1 + r[0][1] for r in rows if r[3] is not None),), dtype=torch.int32, device=dev)
     descs = (_lib.BpCall * len(rows))()
+    # a count mailbox slot per level with a list, or none at all (an empty list has no publisher; PendingLevels reads either
+    # every level's slot or the one tensor)
+    listed = [r for r in rows if r[3] is not None]
+    slots = [_lib.mailbox_read(1 + r[0][1]) if r[3][0].shape[0] > 0 else None for r in listed]
+    slots = iter(slots if all(m is not None for m in slots) else [None] * len(listed))
     handles, off = [], 0
     for d, (shape, feats_c, layout, inputs, voxel_size, min_view, mode) in zip(descs, rows):
         v, b, c, h, w = shape
@@ -230,7 +253,10 @@ def prepare_levels_async(levels, stream=None):
         if inputs is None:
             handles.append(PreparedMaps(nhwc, (ws, feats_c), stream))
             continue
-        hd = CountedBackProject(shape, inputs + (voxel_size, min_view, mode), d, count, n_valid_dev, ws, stream)
+        mb = next(slots)
+        if mb is not None:      # (published by the level's gather half, or by the scan launch of a long list, queued here)
+            d.counts_host, d.counts_seq = mb.payload_dev, mb.seq
+        hd = CountedBackProject(shape, inputs + (voxel_size, min_view, mode), d, count, n_valid_dev, ws, stream, mailbox=mb)
         hd.nhwc, hd.feats, hd.n_valid_all, hd.n_valid_off = nhwc, feats_c, n_valid_all, off
         handles.append(hd)
         off += 1 + b
@@ -238,6 +264,9 @@ def prepare_levels_async(levels, stream=None):
     def queue():
         _lib.check(lib.eprecon_back_project_prepare_levels_async(ctypes.byref(descs), len(rows), _lib.current_stream()),
                    "eprecon_back_project_prepare_levels_async")
+        for hd in handles:
+            if getattr(hd, "mailbox", None) is not None:
+                hd.mailbox.queued(hd.n_valid_dev)
     if stream is None:
         queue()
     else:
@@ -271,14 +300,23 @@ def run_async(coords, origin, voxel_size, feats, krcam, min_view, mode=MODE_MEAN
     else:
         n_valid_dev = torch.empty((1 + b + int(extra_words),), dtype=torch.int32, device=dev)
         ws = _lib.workspace(lib.eprecon_back_project_workspace_bytes(n, b, v, c, h, w, layout), dev)
+    # The counts' way to the host: the count mailbox slot the count half took (counted.mailbox), else one taken here unless the
+    # caller reads the counts itself (hold_read) or nobody would publish (an empty list); without a slot, a pinned copy.
+    mb, early = (counted.mailbox, counted.early) if counted is not None else (None, False)
+    if mb is None and not hold_read and n > 0:
+        mb = _lib.mailbox_read(1 + b)
     if counted is not None:     # the descriptor of the count half, with the maps and the outputs
         call = _lib.BpCall.from_buffer_copy(counted.call)
         call.feats, call.feats_layout = _lib.ptr(feats_c), layout
         _set_outputs(call, t, rank_out, phase=2)
     else:
         call = _call(inputs, feats_c, shape, layout, voxel_size, min_view, mode, t, n_valid_dev, ws, rank_out)
+    # (early: the count half has published already; the gather half writes the same counts to the device and is handed no slot)
+    call.counts_host, call.counts_seq = (mb.payload_dev, mb.seq) if mb is not None and not early else (None, 0)
     _lib.check(lib.eprecon_back_project_call_async(ctypes.byref(call), _lib.current_stream()), "eprecon_back_project_call_async")
-    read = None if hold_read else _lib.PinnedRead(n_valid_dev[:1 + b])
+    if mb is not None and not early:
+        mb.queued(n_valid_dev)
+    read = None if hold_read else mb if mb is not None else _lib.PinnedRead(n_valid_dev[:1 + b])
     # inputs stay referenced until result(): the kernels may still be reading them
     t["_keep"] = (*inputs, feats_c, n_valid_dev, ws if counted is not None else None)
     pend = PendingBackProject(t, n, v, c, b, int(min_valid_per_batch), read, want_grid, want_mean)

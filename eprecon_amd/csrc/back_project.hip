@@ -105,6 +105,8 @@ int bp_validate(const eprecon_bp_call &a, BpRole role)
     if (!a.workspace || (!a.feats && !(listed && !rows && nhwc))) return EPRECON_ERR_ARG;   // (a count reads no channels-last maps)
     if (listed && (!a.origin || !a.krcam || !a.n_valid_dev)) return EPRECON_ERR_ARG;
     if (listed && a.n > 0 && (!a.coords || !a.count || (rows && (!a.out_feats || !a.out_coords)))) return EPRECON_ERR_ARG;
+    // a count mailbox: there has to be a publisher (a list with entries), a sequence number, and room for 1 + B words
+    if (a.counts_host && (!listed || a.n == 0 || a.counts_seq == 0 || 1 + a.batch > EPRECON_MAILBOX_WORDS)) return EPRECON_ERR_ARG;
     if ((size_t)a.n_views * a.batch * 12 * sizeof(float) > 32 * 1024) return EPRECON_ERR_UNSUPPORTED;
     if (a.workspace_bytes < eprecon_back_project_workspace_bytes(a.n, a.batch, a.n_views, a.channels, a.height, a.width,
                                                                  a.feats_layout))
@@ -158,6 +160,7 @@ BpPlan bp_plan(const eprecon_bp_call &a)
     p.count = a.count; p.out_grid = a.out_grid; p.out_mask = a.out_mask; p.n_valid_dev = a.n_valid_dev;
     p.block_offsets = pl.tile_sums;
     p.rank = a.phase == EPRECON_BP_COUNT ? nullptr : a.rank;   // (the count half writes no rows)
+    p.counts_host = a.counts_host; p.counts_seq = a.counts_seq;
     // EPRECON_BP_XCD_SLABS=0 (read per call): the gather's tiles in hardware block order — round-robin over the eight XCDs, so
     // every XCD's L2 sees tiles from the whole volume — instead of one contiguous slab of the raster per XCD.  Same results.
     p.xcd_slabs = ep::switch_off("EPRECON_BP_XCD_SLABS") ? 0 : 1;
@@ -187,18 +190,23 @@ int bp_clear_counters(const eprecon_bp_call &a, hipStream_t st)
     return EPRECON_OK;
 }
 
-// the scan launch of a list whose gather does not fold it in: exclusive scan of the tile totals, the counters
-int bp_launch_scan(const BpPlan &pl, hipStream_t st)
+// the scan launch of a list whose gather does not fold it in: exclusive scan of the tile totals, the counters (and the call's
+// count mailbox).  write_back = false: the early publish of a count half -- the counters and the mailbox only, the totals stay raw
+int bp_launch_scan(const BpPlan &pl, hipStream_t st, bool write_back = true)
 {
     hipLaunchKernelGGL(bp_scan_kernel, dim3(1), dim3(1024), 0, st, pl.tile_sums, pl.ntile, pl.p.n_valid_dev,
-                       (const int32_t *)pl.blk_batch, pl.nblk_count, pl.p.batch);
+                       (const int32_t *)pl.blk_batch, pl.nblk_count, pl.p.batch, write_back ? 1 : 0, pl.p.counts_host,
+                       pl.p.counts_seq);
     EP_LAUNCH_CHECK();
     return EPRECON_OK;
 }
 
-// the counters' memset where one is needed, then prepare (re-layout + count in one grid) or [re-layout,] count, then the scan
+// the counters' memset where one is needed, then prepare (re-layout + count in one grid) or [re-layout,] count, then the scan.
+// early_publish: a count half with a count mailbox whose gather folds the scan in -- the counts are final once the count has
+// run, so one workgroup sums the totals (leaving them raw) and publishes here, on the stream the count half was given, long
+// before the gather half writes the same values again
 template <int VOX>
-int bp_queue_count(const eprecon_bp_call &a, const BpPlan &pl, hipStream_t st)
+int bp_queue_count(const eprecon_bp_call &a, const BpPlan &pl, hipStream_t st, bool early_publish)
 {
     const BpParams &p = pl.p;
     if (a.n == 0 || (pl.chain4 && !pl.clear_in_relayout)) {
@@ -228,7 +236,8 @@ int bp_queue_count(const eprecon_bp_call &a, const BpPlan &pl, hipStream_t st)
         hipLaunchKernelGGL((bp_count_kernel<VOX>), dim3(pl.nblk_count), dim3(256), pl.lds_count, st, p, pl.tile_sums, pl.blk_batch);
     }
     EP_LAUNCH_CHECK();
-    return p.fold ? EPRECON_OK : bp_launch_scan(pl, st);
+    if (!p.fold) return bp_launch_scan(pl, st);
+    return early_publish && p.counts_host ? bp_launch_scan(pl, st, false) : EPRECON_OK;
 }
 
 // the gather inside the profile bracket, then the depth normalisation of MEAN_DEPTH
@@ -254,11 +263,11 @@ int bp_queue_gather(const eprecon_bp_call &a, const BpPlan &pl, hipStream_t st)
 }
 
 // the launches of a validated and planned descriptor: both halves, or the one `phase` names
-int bp_queue(const eprecon_bp_call &a, const BpPlan &pl, hipStream_t st)
+int bp_queue(const eprecon_bp_call &a, const BpPlan &pl, hipStream_t st, bool early_publish = false)
 {
     return pick<256, 64, 16>(pl.vox, [&](auto vox) {   // the one place where the tile size becomes a template argument
         constexpr int VOX = decltype(vox)::value;
-        const int rc = a.phase != EPRECON_BP_GATHER ? bp_queue_count<VOX>(a, pl, st) : EPRECON_OK;
+        const int rc = a.phase != EPRECON_BP_GATHER ? bp_queue_count<VOX>(a, pl, st, early_publish) : EPRECON_OK;
         return rc != EPRECON_OK || a.phase == EPRECON_BP_COUNT ? rc : bp_queue_gather<VOX>(a, pl, st);
     });
 }
@@ -389,7 +398,7 @@ int eprecon_back_project_call_async(const eprecon_bp_call *call, void *stream)
 {
     if (!call || (call->phase != 0 && call->phase != EPRECON_BP_COUNT && call->phase != EPRECON_BP_GATHER)) return EPRECON_ERR_ARG;
     const int rc = bp_validate(*call, (BpRole)call->phase);
-    return rc != EPRECON_OK ? rc : bp_queue(*call, bp_plan(*call), (hipStream_t)stream);
+    return rc != EPRECON_OK ? rc : bp_queue(*call, bp_plan(*call), (hipStream_t)stream, call->phase == EPRECON_BP_COUNT);
 }
 
 int eprecon_back_project_call(const eprecon_bp_call *call, int min_valid_per_batch, int32_t *n_valid_host, void *stream)

@@ -34,6 +34,8 @@ struct BpParams {
     int nblk_count;
     int xcd_slabs;  // 1 (default): every XCD walks one contiguous range of tiles (ep::xcd_remap); 0: tile = hardware block id
     int32_t *rank;  // [n + 1] or null: list entry -> output row or -1, then one word 0 (eprecon_bp_call::rank)
+    int32_t *counts_host;  // count mailbox (eprecon_bp_call::counts_host / counts_seq) or null: whoever writes n_valid_dev[0 .. B]
+    uint32_t counts_seq;   // publishes the same words there (ep::mailbox_publish)
 };
 
 // Cheap projection with bit-exact visibility.  The fma chains for (px, py, pz) are the contract's;
@@ -151,10 +153,13 @@ __global__ __launch_bounds__(256) void bp_count_kernel(BpParams p, int32_t *tile
     count_body<VOX>(smem, p, tile_sums, blk_batch, (int)blockIdx.x);
 }
 
-// exclusive scan of the block totals, one workgroup; also publishes n_valid
+// exclusive scan of the block totals, one workgroup; also publishes n_valid -- to n_valid_dev[0 .. batch] and, for a call with
+// a count mailbox (mb_payload, mb_seq), to the host.  write_back = 0: the totals are left as they are (the early publish of a
+// count half whose gather folds the scan in and wants the raw totals): only the counters are written.
 __global__ __launch_bounds__(1024) void bp_scan_kernel(int32_t *block_sums, int nblk,
                                                        int32_t *n_valid_dev, const int32_t *blk_batch = nullptr,
-                                                       int nblk_count = 0, int batch = 0)
+                                                       int nblk_count = 0, int batch = 0, int write_back = 1,
+                                                       int32_t *mb_payload = nullptr, uint32_t mb_seq = 0)
 {
     __shared__ int sWave[1024 / kWave];
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid / kWave;
@@ -177,7 +182,7 @@ __global__ __launch_bounds__(1024) void bp_scan_kernel(int32_t *block_sums, int 
             woff += (w < wid) ? c : 0;
             tot += c;
         }
-        if (i < nblk) block_sums[i] = carry + woff + x - v;
+        if (write_back && i < nblk) block_sums[i] = carry + woff + x - v;
         carry += tot;
         __syncthreads();
     }
@@ -201,6 +206,7 @@ __global__ __launch_bounds__(1024) void bp_scan_kernel(int32_t *block_sums, int 
             }
         }
     }
+    if (tid == 0 && mb_payload) mailbox_publish(mb_payload, mb_seq, n_valid_dev, 1 + batch);   // (its own stores, read back)
 }
 
 // zero / zero_n (optional): int32 words the first block clears on its way — the valid-voxel counters of the back-projection

@@ -19,7 +19,8 @@ namespace {
 // no ticket, no spin: nothing here waits for another workgroup.
 //   tile_base_partials   before phase 1: per-wave partial sums -> sFold (2 x BLOCK/64 ints)
 //   tile_base_finish     after the next barrier of the caller (block_exclusive_rank's): the sums; the workgroup
-//                        of the last tile publishes n_valid_dev[0 .. B] (what bp_scan_kernel published), and
+//                        of the last tile publishes n_valid_dev[0 .. B] (what bp_scan_kernel published; its thread 0
+//                        also hands them to the host through the call's count mailbox, when it has one), and
 //                        has to do so before the caller's `if (nloc == 0) return;`
 // `all` (block-uniform): the sum runs over every tile, which also gives n_valid -- wanted by that last workgroup
 // and by every workgroup when out_grid / out_mask are written (n_valid is their view stride).
@@ -87,6 +88,7 @@ __device__ __forceinline__ TileBase tile_base_finish(const BpParams &p, int lb, 
                 }
             }
         }
+        if (tid == 0 && p.counts_host) mailbox_publish(p.counts_host, p.counts_seq, p.n_valid_dev, 1 + p.batch);
     }
     return r;
 }

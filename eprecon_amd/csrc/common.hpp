@@ -75,6 +75,17 @@ __device__ __forceinline__ int xcd_remap(int hw_bid, int nblk)
     return start + k;
 }
 
+// The count mailbox, device side (count_mailbox.hip; eprecon_mailbox_slot::payload_dev and ::seq): called by ONE thread -- the
+// one that has just written the same n words to device memory -- it stores them into the slot's payload (host-coherent pinned
+// memory), fences at system scope, and release-stores the sequence word in front of the payload, which is what the host
+// spins on.  Stores only: nothing on the device reads the mailbox or waits for the host.
+__device__ __forceinline__ void mailbox_publish(int32_t *payload, uint32_t seq, const int32_t *values, int n)
+{
+    for (int i = 0; i < n; ++i) payload[i] = values[i];
+    __threadfence_system();
+    __hip_atomic_store(reinterpret_cast<uint32_t *>(payload) - 1, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // Exclusive rank of this thread among the threads of its block for which `pred` holds, by wave
 // ballot + popcount and a per-wave count table in LDS (`wave_counts` holds BLOCK/64 ints).
 // Contains one __syncthreads(); every thread of the block must call it.

@@ -69,9 +69,11 @@ __device__ __forceinline__ uint32_t box_columns(const uint32_t *vol, int D, int 
     return r & zmask;
 }
 
-__global__ __launch_bounds__(kSelThreads) void init_select_kernel(const unsigned char *marks, int batch, int D,
+// (amdgpu_waves_per_eu: the two mailbox arguments took the scalar registers from 99 to 103, one past what eight waves per SIMD
+// leave each wave; the compiler is asked to stay within them)
+__global__ __launch_bounds__(kSelThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void init_select_kernel(const unsigned char *marks, int batch, int D,
                                                                   int out_scale, int4 *out_coords,
-                                                                  int32_t *n_out_dev)
+                                                                  int32_t *n_out_dev, int32_t *mb_payload, uint32_t mb_seq)
 {
     __shared__ uint32_t va[1024], vb[1024];
     __shared__ int sWave[kSelThreads / kWave];
@@ -118,7 +120,11 @@ __global__ __launch_bounds__(kSelThreads) void init_select_kernel(const unsigned
         written += tot;
         __syncthreads();
     }
-    if (tid == 0) n_out_dev[0] = written;
+    if (tid == 0) {
+        n_out_dev[0] = written;
+        // the count mailbox of the call, when it has one: the thread that wrote every word of the counters hands them to the host
+        if (mb_payload) mailbox_publish(mb_payload, mb_seq, n_out_dev, 1 + batch);
+    }
 }
 
 __global__ __launch_bounds__(256) void upsample_coords_kernel(const int4 *coords, int n, int interval,
@@ -149,6 +155,13 @@ __global__ __launch_bounds__(256) void upsample_feat_kernel(const float *feat, i
     up[e] = feat[(row >> 3) * ld + c];
 }
 
+// a selection's count mailbox (or none): a slot as eprecon_mailbox_acquire filled it, with room for the 1 + batch counters
+bool slot_fits(const eprecon_mailbox_slot *slot, int batch)
+{
+    return !slot || (slot->payload_dev && slot->seq != 0 && batch > 0 && slot->words == 1 + batch &&
+                     slot->words <= EPRECON_MAILBOX_WORDS);
+}
+
 }  // namespace
 
 extern "C" {
@@ -162,8 +175,16 @@ int eprecon_init_select_async(const float *logit, const int32_t *coords, int64_t
                               int batch, int dim, int cell, int32_t *out_coords, int32_t *n_out_dev,
                               void *workspace, size_t workspace_bytes, void *stream)
 {
+    return eprecon_init_select_mb_async(logit, coords, n, threshold, batch, dim, cell, out_coords, n_out_dev, workspace,
+                                        workspace_bytes, nullptr, stream);
+}
+
+int eprecon_init_select_mb_async(const float *logit, const int32_t *coords, int64_t n, float threshold, int batch, int dim,
+                                 int cell, int32_t *out_coords, int32_t *n_out_dev, void *workspace, size_t workspace_bytes,
+                                 const eprecon_mailbox_slot *slot, void *stream)
+{
     if (n < 0 || batch <= 0 || dim <= 0 || dim > 32 || cell <= 0 || !out_coords || !n_out_dev || !workspace ||
-        (n > 0 && (!logit || !coords)))
+        (n > 0 && (!logit || !coords)) || !slot_fits(slot, batch))
         return EPRECON_ERR_ARG;
     if (workspace_bytes < eprecon_init_select_workspace_bytes(batch, dim)) return EPRECON_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
@@ -176,7 +197,8 @@ int eprecon_init_select_async(const float *logit, const int32_t *coords, int64_t
         EP_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(init_select_kernel, dim3(1), dim3(kSelThreads), 0, st, (const unsigned char *)marks, batch,
-                       dim, cell, reinterpret_cast<int4 *>(out_coords), n_out_dev);
+                       dim, cell, reinterpret_cast<int4 *>(out_coords), n_out_dev, slot ? slot->payload_dev : (int32_t *)nullptr,
+                       slot ? slot->seq : 0u);
     EP_LAUNCH_CHECK();
     return EPRECON_OK;
 }
@@ -188,13 +210,22 @@ int eprecon_init_select_dense_async(const float *logit, const int32_t *coords, i
                                     int grid_y, int grid_z, int stride, float threshold, int dim, int cell, int32_t *out_coords,
                                     int32_t *n_out_dev, void *workspace, size_t workspace_bytes, void *stream)
 {
+    return eprecon_init_select_dense_mb_async(logit, coords, n, rank, grid_x, grid_y, grid_z, stride, threshold, dim, cell, out_coords,
+                                              n_out_dev, workspace, workspace_bytes, nullptr, stream);
+}
+
+int eprecon_init_select_dense_mb_async(const float *logit, const int32_t *coords, int64_t n, const int32_t *rank, int grid_x,
+                                       int grid_y, int grid_z, int stride, float threshold, int dim, int cell,
+                                       int32_t *out_coords, int32_t *n_out_dev, void *workspace, size_t workspace_bytes,
+                                       const eprecon_mailbox_slot *slot, void *stream)
+{
     if (n < 0 || n > 0x7fffffff || dim <= 0 || dim > 32 || cell <= 0 || stride <= 0 || cell % stride || grid_x <= 0 || grid_y <= 0 ||
         grid_z <= 0 || (int64_t)grid_x * grid_y * grid_z > 0x7ffffff0 || !rank || !out_coords || !n_out_dev || !workspace ||
-        (n > 0 && (!logit || !coords)))
+        (n > 0 && (!logit || !coords)) || !slot_fits(slot, 1))
         return EPRECON_ERR_ARG;
     if (switch_off("EPRECON_INIT_GLUE"))
-        return eprecon_init_select_async(logit, coords, n, threshold, 1, dim, cell, out_coords, n_out_dev, workspace, workspace_bytes,
-                                         stream);
+        return eprecon_init_select_mb_async(logit, coords, n, threshold, 1, dim, cell, out_coords, n_out_dev, workspace,
+                                            workspace_bytes, slot, stream);
     if (workspace_bytes < eprecon_init_select_workspace_bytes(1, dim)) return EPRECON_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     unsigned char *marks = reinterpret_cast<unsigned char *>(workspace);
@@ -202,7 +233,8 @@ int eprecon_init_select_dense_async(const float *logit, const int32_t *coords, i
                        grid_x, grid_y, grid_z, cell / stride, threshold, dim, marks);
     EP_LAUNCH_CHECK();
     hipLaunchKernelGGL(init_select_kernel, dim3(1), dim3(kSelThreads), 0, st, (const unsigned char *)marks, 1, dim, cell,
-                       reinterpret_cast<int4 *>(out_coords), n_out_dev);
+                       reinterpret_cast<int4 *>(out_coords), n_out_dev, slot ? slot->payload_dev : (int32_t *)nullptr,
+                       slot ? slot->seq : 0u);
     EP_LAUNCH_CHECK();
     return EPRECON_OK;
 }

@@ -1,13 +1,16 @@
 """Host wrappers for the dense-grid helpers (csrc/grid_ops.hip)."""
+import ctypes
+
 import torch
 
 from . import _lib
 
 
-def _queue_select(logit, coords, batch_size, dim, cell, threshold, dense):
+def _queue_select(logit, coords, batch_size, dim, cell, threshold, dense, mailbox=None):
     """the selection's launches -> (out int32[batch dim^3, 4], counts int32[1 + batch]), both on the device.
     dense (optional, one batch element): the sparse.DenseMap of the voxel set `coords` — its rank volume stands in for the
-    list when the marks are made (eprecon_init_select_dense_async)"""
+    list when the marks are made (eprecon_init_select_dense_async)
+    mailbox (optional): a _lib.MailboxRead of 1 + batch words — the counts are also published into its slot"""
     lib = _lib.load()
     logit = logit.reshape(-1).contiguous()
     coords = coords.contiguous()
@@ -16,18 +19,19 @@ def _queue_select(logit, coords, batch_size, dim, cell, threshold, dense):
     out = torch.empty((batch_size * dim ** 3, 4), dtype=torch.int32, device=dev)
     counts = torch.empty(1 + batch_size, dtype=torch.int32, device=dev)      # (init_select_kernel writes every word)
     ws = _lib.workspace(lib.eprecon_init_select_workspace_bytes(batch_size, dim), dev)
+    slot = None if mailbox is None else ctypes.byref(mailbox.slot)
     if dense is not None and batch_size == 1 and cell % dense.vset.stride == 0:
         assert dense.vset.n == coords.shape[0]
         gx, gy, gz = dense.dims
-        _lib.check(lib.eprecon_init_select_dense_async(_lib.ptr(logit), _lib.ptr(coords), coords.shape[0], _lib.ptr(dense.rank),
-                                                       gx, gy, gz, dense.vset.stride, float(threshold), dim, cell, _lib.ptr(out),
-                                                       _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.current_stream()),
-                   "eprecon_init_select_dense_async")
+        _lib.check(lib.eprecon_init_select_dense_mb_async(_lib.ptr(logit), _lib.ptr(coords), coords.shape[0], _lib.ptr(dense.rank),
+                                                          gx, gy, gz, dense.vset.stride, float(threshold), dim, cell, _lib.ptr(out),
+                                                          _lib.ptr(counts), _lib.ptr(ws), ws.numel(), slot, _lib.current_stream()),
+                   "eprecon_init_select_dense_mb_async")
     else:
-        _lib.check(lib.eprecon_init_select_async(_lib.ptr(logit), _lib.ptr(coords), coords.shape[0],
-                                                 float(threshold), batch_size, dim, cell, _lib.ptr(out),
-                                                 _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.current_stream()),
-                   "eprecon_init_select_async")
+        _lib.check(lib.eprecon_init_select_mb_async(_lib.ptr(logit), _lib.ptr(coords), coords.shape[0],
+                                                    float(threshold), batch_size, dim, cell, _lib.ptr(out),
+                                                    _lib.ptr(counts), _lib.ptr(ws), ws.numel(), slot, _lib.current_stream()),
+                   "eprecon_init_select_mb_async")
     return out, counts
 
 
@@ -54,9 +58,11 @@ class PendingSelect:
 
 
 def init_select_async(logit, coords, batch_size, dim=24, cell=4, threshold=0.3, dense=None):
-    """init_select without the host round trip: -> PendingSelect"""
-    out, counts = _queue_select(logit, coords, batch_size, dim, cell, threshold, dense)
-    return PendingSelect(out, _lib.PinnedRead(counts))
+    """init_select without the host round trip: -> PendingSelect (the counts come through the count mailbox when a slot is to
+    be had, else through a pinned copy queued behind the selection)"""
+    mb = _lib.mailbox_read(1 + batch_size)
+    out, counts = _queue_select(logit, coords, batch_size, dim, cell, threshold, dense, mb)
+    return PendingSelect(out, _lib.PinnedRead(counts) if mb is None else mb.queued(counts))
 
 
 def upsample(pre_feat, pre_coords, interval, up_coords=None):

@@ -36,6 +36,7 @@ extern "C" {
 #define EPRECON_ERR_ARG (-1)
 #define EPRECON_ERR_WORKSPACE (-2)
 #define EPRECON_ERR_UNSUPPORTED (-3)
+#define EPRECON_ERR_TIMEOUT (-4)      /* eprecon_mailbox_wait: the count was not published within the cap */
 #define EPRECON_ERR_HIP_BASE (-1000)
 
 /* goes up when an exported function keeps its name with another argument list: the loader refuses a library of another version */
@@ -43,6 +44,40 @@ extern "C" {
 int eprecon_abi_version(void);
 /* name of the gfx target the kernels were compiled for, e.g. "gfx950" */
 const char *eprecon_build_arch(void);
+
+/* ------------------------------------------------------------------------------------------
+ * Count mailbox: a kernel's final counts reach the host through host-coherent pinned memory instead of a device-to-host copy
+ * queued behind the kernel (no copy launch, no event, nothing on the stream).  One ring of 64 slots per process, allocated at
+ * the first acquire; a slot carries at most EPRECON_MAILBOX_WORDS int32.  Thread-safe.
+ *
+ *   eprecon_mailbox_acquire  fills `out`: EPRECON_OK; EPRECON_EMPTY when no slot is to be had (the ring is full, words >
+ *                            EPRECON_MAILBOX_WORDS, or EPRECON_COUNT_MAILBOX=0) -- the caller then copies the counts as before.
+ *   a launch that takes a mailbox (eprecon_bp_call::counts_host / counts_seq, eprecon_init_select*_mb_async) is handed
+ *                            payload_dev and seq; the thread that writes the final count to device memory stores the same
+ *                            words at payload_dev[0 ..] and then seq into the slot's sequence word.  Set `armed` once such
+ *                            a launch has been queued.  Nothing on the device waits for or reads the mailbox.
+ *   eprecon_mailbox_wait     host spin (pause, then yield) until the slot's sequence word equals `seq`, at most timeout_us;
+ *                            EPRECON_OK: out[0 .. words) holds the counts; EPRECON_ERR_TIMEOUT otherwise (callers use a cap
+ *                            of 2 s -- far above any step -- and then synchronise the stream and read the device words).
+ *   eprecon_mailbox_release  returns the slot, read or not.  A slot that is armed and not published yet is handed out again
+ *                            only after its publisher has stored.
+ *   eprecon_count_mailbox    1, or 0 under EPRECON_COUNT_MAILBOX=0 (read once, when the library is loaded).
+ *   eprecon_mailbox_free_slots  slots that an acquire could hand out right now (diagnostics, tests).
+ * ------------------------------------------------------------------------------------------ */
+#define EPRECON_MAILBOX_WORDS 15
+typedef struct eprecon_mailbox_slot {
+    int32_t *payload_dev;         /* what the publishing launch is handed (the sequence word is the int32 in front of it) */
+    const int32_t *payload_host;  /* the same words as the host sees them */
+    uint32_t seq;                 /* never 0; rises per slot */
+    int32_t index;                /* slot in the ring */
+    int32_t words;                /* as asked for */
+    int32_t armed;                /* set by the caller once a publishing launch is queued */
+} eprecon_mailbox_slot;
+int eprecon_count_mailbox(void);
+int eprecon_mailbox_acquire(int words, eprecon_mailbox_slot *out);
+int eprecon_mailbox_wait(const eprecon_mailbox_slot *slot, int64_t timeout_us, int32_t *out);
+int eprecon_mailbox_release(const eprecon_mailbox_slot *slot);
+int eprecon_mailbox_free_slots(void);
 
 /* ------------------------------------------------------------------------------------------
  * Multi-view back-projection  (K1 project+mask+count, K2 stable compaction, K3 bilinear
@@ -106,6 +141,15 @@ typedef struct eprecon_bp_call {
      * would build from the call's out_coords (its trailing word counts voxels off the grid: none here).  An output of this call
      * like the others: the count half ignores it, batch != 1 is EPRECON_ERR_ARG before any launch, n == 0 clears rank[0]. */
     int32_t *rank;
+    /* The count mailbox (above): eprecon_mailbox_slot::payload_dev and ::seq of a slot of 1 + batch words, or NULL and 0.  The
+     * thread that writes n_valid_dev[0 .. batch] -- in the scan launch of a long list, else in the gather's last workgroup --
+     * publishes the same words there.  A count half (phase EPRECON_BP_COUNT) that carries one publishes EARLY: it also queues
+     * the one-workgroup scan of its tile totals behind the count on its stream, which leaves the totals as they are and writes
+     * and publishes n_valid_dev[0 .. batch]; the gather half (which writes the same values again) is then handed no mailbox.
+     * Needs n > 0 (an empty list has no publisher) and 1 + batch <= EPRECON_MAILBOX_WORDS, else EPRECON_ERR_ARG.  The levels of
+     * eprecon_back_project_prepare_levels_async carry the fields for their gather halves (and for their scan launches). */
+    int32_t *counts_host;
+    uint32_t counts_seq;
 } eprecon_bp_call;
 
 /* Stream-ordered; does not synchronise.  The whole call or the half `phase` names. */
@@ -538,6 +582,17 @@ int eprecon_init_select_dense_async(const float *logit, const int32_t *coords, i
                                     int grid_y, int grid_z, int stride, float threshold, int dim, int cell,
                                     int32_t *out_coords, int32_t *n_out_dev, void *workspace, size_t workspace_bytes,
                                     void *stream);
+/*
+ * The two selections with a count mailbox: the thread that writes the last word of n_out_dev[0 .. batch] also publishes them
+ * into `slot` (eprecon_mailbox_acquire(1 + batch, ...); 1 + batch words).  slot == NULL: the calls above, which forward here.
+ */
+int eprecon_init_select_mb_async(const float *logit, const int32_t *coords, int64_t n, float threshold, int batch, int dim,
+                                 int cell, int32_t *out_coords, int32_t *n_out_dev, void *workspace, size_t workspace_bytes,
+                                 const eprecon_mailbox_slot *slot, void *stream);
+int eprecon_init_select_dense_mb_async(const float *logit, const int32_t *coords, int64_t n, const int32_t *rank, int grid_x,
+                                       int grid_y, int grid_z, int stride, float threshold, int dim, int cell,
+                                       int32_t *out_coords, int32_t *n_out_dev, void *workspace, size_t workspace_bytes,
+                                       const eprecon_mailbox_slot *slot, void *stream);
 /*
  * Sparsify for the next stage (models/neucon_network.py:454-507) in one call: occupancy = occ > threshold; the kept rows of
  * coords / tsdf / occ / feat_all compacted in row order (torch.nonzero + index_select + cat of the reference) and the counts
