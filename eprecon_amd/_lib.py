@@ -173,6 +173,11 @@ SIGNATURES = {
     "eprecon_segment_stats_lds_segments": (_c.c_int32, []),
     "eprecon_segment_moments_async": (_i, [_vp, _vp, _i64, _c.c_int32, _vp, _vp, _vp]),
     "eprecon_segment_extents_async": (_i, [_vp, _vp, _i64, _c.c_int32, _vp, _vp, _vp, _vp]),
+    "eprecon_simplify_max_clusters": (_c.c_int32, []),
+    "eprecon_simplify_keys_async": (_i, [_vp, _i64, _vp, _c.c_double, _vp, _vp, _vp]),
+    "eprecon_simplify_faces_async": (_i, [_vp, _i64, _vp, _i64, _c.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "eprecon_simplify_quadrics_async": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_int32, _vp, _c.c_double,
+                                             _c.c_double, _vp, _vp, _vp, _vp]),
     "eprecon_nearest_voxel_async": (_i, [_vp, _c.c_uint32, _vp, _i64, _vp, _i64, _i, _vp, _vp]),
     "eprecon_upsample2x_nhwc_async": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "eprecon_decoder_keys_async": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp]),

@@ -2,6 +2,7 @@
 
     python -m eprecon_amd.reconstruct --data_path DIR [--source_path DIR] [--mode test|val] [--ckpt FILE] --out DIR \\
            [--scenes FILE] [--n_views 9] [--size 640 480] [--host-views] [--color] [--clean N [--clean_segments N]] [--objects]
+           [--simplify CELL]
 
 reads <data_path>/all_tsdf_<n_views>_1/fragments_<mode>.pkl (eprecon_amd.generate_gt writes it) and the frames it names
 (scannet.ScanNetDataset), and walks the fragments in file order, one per step: PrepareViews -> RandomTransformSpace (no
@@ -28,6 +29,10 @@ the cleaned <scene>.npz and its three meshes into clean/ beside the saved scene;
 
 --objects (off by default) writes <scene>_objects.json beside every saved scene once it is written: one record per segment
 with its voxel count, centroid, axis-aligned box and upright oriented box (eprecon_amd.scene_objects); no other file changes.
+
+--simplify CELL (off by default) writes the three meshes of every saved scene once more, simplified by quadric vertex
+clustering in cells of CELL metres (eprecon_amd.simplify), as <scene>_lod.ply, mesh_semantic_<scene>_lod.ply and
+mesh_instance_<scene>_lod.ply beside them; no other file changes.
 """
 import argparse
 import os
@@ -76,6 +81,8 @@ def parse_args(argv=None):
     ap.add_argument("--clean_segments", default=0, type=int, metavar="N", help="with --clean: pieces of a segment of fewer "
                                                                                 "than N voxels lose their ids")
     ap.add_argument("--objects", action="store_true", help="also write <scene>_objects.json: count, centroid and boxes per segment")
+    ap.add_argument("--simplify", type=float, metavar="CELL", help="also write the scene's meshes simplified by vertex clustering "
+                                                                   "in cells of CELL metres, as *_lod.ply")
     return ap.parse_args(argv)
 
 
@@ -144,6 +151,16 @@ def describe_saved_scenes(outputs, saver, epoch):
         if os.path.exists(npz):
             path = os.path.join(save_path, scene + "_objects.json")
             print(f"[reconstruct] {format_objects(name, describe_scene(npz, path), path)}")
+
+
+def simplify_saved_scenes(outputs, saver, epoch, cell):
+    """--simplify: the meshes of the scenes this step saved, simplified into *_lod.ply beside them"""
+    from .simplify import format_report, simplify_scene
+    save_path = "{}_fusion_eval_{}".format(saver.log_dir, epoch)
+    for name in outputs.get("scene_name", []):
+        npz = os.path.join(save_path, name.replace("/", "-") + ".npz")
+        if os.path.exists(npz):
+            print(f"[reconstruct] {format_report(name, simplify_scene(npz, save_path, cell)[0])}")
 
 
 def main(argv=None):
@@ -220,6 +237,8 @@ def main(argv=None):
                 clean_saved_scenes(outputs, saver, epoch, args.clean, args.clean_segments)
             if args.objects:
                 describe_saved_scenes(outputs, saver, epoch)
+            if args.simplify is not None:
+                simplify_saved_scenes(outputs, saver, epoch, args.simplify)
             count += 1
         torch.cuda.synchronize(device)
         report(scene, count, time.perf_counter() - t_scene, read_s, prepare_s)

@@ -1174,6 +1174,41 @@ int eprecon_segment_extents_async(const int32_t *coords, const int32_t *rank, in
                                   double *ext, int32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mesh simplification: quadric vertex clustering  (csrc/mesh_simplify.hip, eprecon_amd/simplify.py; the reference has no
+ * counterpart, its users run open3d's simplify_vertex_clustering on the .ply: the rule is DESIGN.md 5b's)
+ *
+ * verts f32[n,3], faces int32[m,3] on the device; origin_host double[3] and cell > 0 on the host; n < 2^31 and 3 m < 2^31,
+ * at most eprecon_simplify_max_clusters() = 2^21 clusters, else EPRECON_ERR_UNSUPPORTED before any launch.  status int32[1]
+ * is cleared by the call that takes it and collects: 1 a face index outside [0, n); 2 a vertex that is not finite; 4 a cell
+ * outside [-2^20, 2^20).
+ *
+ * eprecon_simplify_keys_async: key int64[n] = (cx + 2^20) << 42 | (cy + 2^20) << 21 | (cz + 2^20) with
+ *   c = floor((double(v) - origin) / cell) per axis, every operation rounded in fp64; -1 for a vertex with status 2 or 4.
+ * eprecon_simplify_faces_async: cluster int32[n] (the caller's ranks, in [0, n_clusters)) -> tri int32[m,3] the clusters of
+ *   the corners (-1 three times for a face with status 1: such a face has no corner entries); face_key int64[m] the sorted
+ *   triple, 21 bits each (-1 for a face with status 1 or with two equal clusters); referenced uint8[n_clusters] (cleared by
+ *   the call) 1 for every cluster of a face with three different clusters.
+ * eprecon_simplify_quadrics_async: with the CSR lists of eprecon_segment_lists_async over tri (3 m entries) and over
+ *   cluster (n entries): per cluster, relative to the centre origin + (c + 0.5) cell of its cell, the mean of its members,
+ *   the area-weighted plane quadrics (A, b) and the sum of the face normals over its corner entries in ascending order
+ *   (faces of zero area skipped), x* from (A + l I) x = b + l mean with l = regularize trace(A) / 3 (the mean when the trace
+ *   is 0), and pos double[n_clusters,3] = centre + mean + t (x* - mean) with the largest t in [0, 1] that stays in the
+ *   cell's closed box; normal f32[n_clusters,3] the normalised normal sum (0 when its length is 0); with colors uint8[n,3],
+ *   rgb uint8[n_clusters,3] = (2 sum + count) / (2 count) in integers.  One lane per cluster, every sum in list order: the
+ *   same bits on every run.  regularize > 0.
+ * ------------------------------------------------------------------------------------------ */
+int32_t eprecon_simplify_max_clusters(void);
+int eprecon_simplify_keys_async(const float *verts, int64_t n, const double *origin_host, double cell, int64_t *key, int32_t *status,
+                                void *stream);
+int eprecon_simplify_faces_async(const int32_t *faces, int64_t m, const int32_t *cluster, int64_t n, int32_t n_clusters, int32_t *tri,
+                                 int64_t *face_key, uint8_t *referenced, int32_t *status, void *stream);
+int eprecon_simplify_quadrics_async(const float *verts, int64_t n, const int32_t *faces, int64_t m, const uint8_t *colors,
+                                    const int64_t *key, const int32_t *corner_offsets, const int32_t *corner_order,
+                                    const int32_t *member_offsets, const int32_t *member_order, int32_t n_clusters,
+                                    const double *origin_host, double cell, double regularize, double *pos, float *normal, uint8_t *rgb,
+                                    void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Nearest finest-level voxel  (K18)
  *
  * Replaces  torch.cdist + argmin(dim=1)                 models/mask3dformer.py:361-367
