@@ -2,7 +2,7 @@
 
     python -m eprecon_amd.reconstruct --data_path DIR [--source_path DIR] [--mode test|val] [--ckpt FILE] --out DIR \\
            [--scenes FILE] [--n_views 9] [--size 640 480] [--host-views] [--color] [--clean N [--clean_segments N]] [--objects]
-           [--simplify CELL]
+           [--simplify CELL] [--preview]
 
 reads <data_path>/all_tsdf_<n_views>_1/fragments_<mode>.pkl (eprecon_amd.generate_gt writes it) and the frames it names
 (scannet.ScanNetDataset), and walks the fragments in file order, one per step: PrepareViews -> RandomTransformSpace (no
@@ -33,6 +33,10 @@ with its voxel count, centroid, axis-aligned box and upright oriented box (eprec
 --simplify CELL (off by default) writes the three meshes of every saved scene once more, simplified by quadric vertex
 clustering in cells of CELL metres (eprecon_amd.simplify), as <scene>_lod.ply, mesh_semantic_<scene>_lod.ply and
 mesh_instance_<scene>_lod.ply beside them; no other file changes.
+
+--preview (off by default) writes <out>/preview/<scene>/<fragment_id:05d>.png after every fragment: the scene so far, ray-cast
+from its voxel rows (eprecon_amd.raycast) from that fragment's last key-frame camera at the network's image size, shaded by
+instance id modulo the palette; no other file changes.
 """
 import argparse
 import os
@@ -83,6 +87,8 @@ def parse_args(argv=None):
     ap.add_argument("--objects", action="store_true", help="also write <scene>_objects.json: count, centroid and boxes per segment")
     ap.add_argument("--simplify", type=float, metavar="CELL", help="also write the scene's meshes simplified by vertex clustering "
                                                                    "in cells of CELL metres, as *_lod.ply")
+    ap.add_argument("--preview", action="store_true", help="also write preview/<scene>/<fragment_id>.png after every fragment: "
+                    "the scene so far, ray-cast from the fragment's last key-frame camera")
     return ap.parse_args(argv)
 
 
@@ -163,6 +169,20 @@ def simplify_saved_scenes(outputs, saver, epoch, cell):
             print(f"[reconstruct] {format_report(name, simplify_scene(npz, save_path, cell)[0])}")
 
 
+def preview_fragment(model, inputs, meta, out, voxel_size, stride=4):
+    """--preview: the scene map as it stands after this fragment, seen from the fragment's last key-frame camera"""
+    from .raycast import SceneGrid, camera_of_projection, preview
+    from .render import DEFAULT_BACKGROUND, write_png
+    height, width = (int(x) for x in inputs["imgs"].shape[-2:])
+    path = os.path.join(out, "preview", meta["scene"].replace("/", "-"), "{:05d}.png".format(int(meta["fragment_id"])))
+    fusion = model.fuse_to_global._scene
+    if fusion is None or fusion.C is None or fusion.C.shape[0] == 0 or fusion.scene_name != meta["scene"]:
+        return write_png(path, np.full((height, width, 3), DEFAULT_BACKGROUND, np.uint8))
+    so_far = fusion.save_mesh(None, meta["scene"])          # a dict of its own: the step's outputs are not touched
+    k, pose = camera_of_projection(inputs["proj_matrices"].reshape(-1, 3, 4, 4)[-1, 0], float(stride))
+    return preview(SceneGrid.from_outputs(so_far, 0, voxel_size), k, pose, height, width, path)
+
+
 def main(argv=None):
     args = parse_args(argv)
     from .neuralrecon import NeuralRecon
@@ -239,6 +259,8 @@ def main(argv=None):
                 describe_saved_scenes(outputs, saver, epoch)
             if args.simplify is not None:
                 simplify_saved_scenes(outputs, saver, epoch, args.simplify)
+            if args.preview:
+                preview_fragment(model, inputs, meta, args.out, float(cfg.MODEL.VOXEL_SIZE))
             count += 1
         torch.cuda.synchronize(device)
         report(scene, count, time.perf_counter() - t_scene, read_s, prepare_s)

@@ -336,6 +336,30 @@ int eprecon_kernel_map_self_async(const void *table, uint32_t capacity, const in
 size_t eprecon_components_workspace_bytes(int64_t n);
 int eprecon_components_async(const int32_t *nbr, int64_t n, const int32_t *keys, int connectivity, int32_t *label, int32_t *status,
                              void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Ray casting of a sparse TSDF scene from its voxel rows (csrc/tsdf_raycast.hip; the reference meshes a scene to show it:
+ * the rule is DESIGN.md §5b "ray-cast surface", the caller eprecon_amd/raycast.py).
+ *   coords  int32[m,3] voxel rows (no batch column; c - 1 .. c + 1 must be keys of the hash grid), tsdf f32[m]
+ *   grid    eprecon_raycast_workspace_bytes(m) bytes, 256-byte aligned, owned by the caller: an int32 header (word 0 the build's
+ *           status: bit 0 a coordinate out of range, bit 1 a table full; words 1..3 / 4..6 the smallest / largest active cell,
+ *           INT_MAX / INT_MIN when no row has tsdf <= 0), the row table (key -> first row) and the brick table (4x4x4-cell
+ *           bricks, brick = cell >> 2, a 64-bit word with bit x + 4 y + 16 z per active cell).  Nothing is allocated inside.
+ * eprecon_raycast_build_async: two launches (clear, build); m == 0 only clears.
+ * eprecon_raycast_async (m >= 1, the grid of a build over the same m rows):
+ *   cams    fp64: K[9], K^-1[9], world -> camera [3x4] per view (eprecon_render_visibility_async's block), then origin[3] and
+ *           1 / voxel_size
+ *   depth f32[V,H,W] camera-z metres (0: nothing hit), normal f32[V,H,W,3] unit, world frame, towards positive TSDF (0),
+ *   row int32[V,H,W] index of the hit cell's row corner nearest the hit point (-1)
+ *   status int32[1] (device): cleared and written by every call; bit 0 / bit 1 when a bounded walk (cells of a brick / bricks
+ *           of the box) gave up: the pixel is empty then, and the caller that reads it raises.
+ * One launch, no atomics: the images are bit-identical from run to run and however the views are split into calls.
+ */
+size_t eprecon_raycast_workspace_bytes(int64_t m);
+int eprecon_raycast_build_async(const int32_t *coords, const float *tsdf, int64_t m, void *grid, size_t grid_bytes, void *stream);
+int eprecon_raycast_async(const void *grid, int64_t m, const float *tsdf, const double *cams, int n_views, int height, int width,
+                          float pixel_center, float znear, float zfar, int refine, float *depth, float *normal, int32_t *row,
+                          int32_t *status, void *stream);
 /* ------------------------------------------------------------------------------------------
  * Kernel maps and sparse convolution  (K5, K10, K11, K13)
  *
