@@ -4,7 +4,8 @@ forms of SURVEY.md appendix A.2, independently of oracle/ and eprecon_amd/: no k
 
 A sparse set of (b, x, y, z) rows is embedded in a dense [B, C, X, Y, Z] volume (absent voxels hold 0), the convolutions are
 F.conv3d / F.conv_transpose3d on that volume read back at the active sites, voxels are numbered by a Python dict in
-first-occurrence order, and every sum is float64."""
+first-occurrence order, and every sum is float64.  (The differentiable blocks take a `dtype`, float64 unless said otherwise:
+tests/pointvoxel_modules_ref.py runs the same formulation in float32 to measure what that precision alone costs.)"""
 import math
 
 import numpy as np
@@ -14,8 +15,9 @@ import torch.nn.functional as F
 F64 = torch.float64
 
 
-def _t64(a):
-    return a.to(F64) if torch.is_tensor(a) else torch.from_numpy(np.asarray(a, np.float64))
+def _t64(a, dtype=F64):
+    """a as a tensor of `dtype` (float64 unless a caller asks for the same formulation in another precision)"""
+    return a.to(dtype) if torch.is_tensor(a) else torch.from_numpy(np.asarray(a, np.float64)).to(dtype)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -49,11 +51,11 @@ class Frame:
         d = self.side // stride
         return torch.from_numpy(((c[:, 0] * d + xyz[:, 0]) * d + xyz[:, 1]) * d + xyz[:, 2])
 
-    def embed(self, coords, feat, stride=1):
+    def embed(self, coords, feat, stride=1, dtype=F64):
         """feat [N, C] at the rows `coords` -> float64 volume [B, C, D, D, D] (D = side / stride), differentiable in feat"""
-        feat = _t64(feat)
+        feat = _t64(feat, dtype)
         d = self.side // stride
-        vol = torch.zeros((self.batch * d ** 3, feat.shape[1]), dtype=F64).index_add(0, self.flat(coords, stride), feat)
+        vol = torch.zeros((self.batch * d ** 3, feat.shape[1]), dtype=dtype).index_add(0, self.flat(coords, stride), feat)
         return vol.reshape(self.batch, d, d, d, -1).permute(0, 4, 1, 2, 3)
 
     def read(self, vol, coords, stride=1):
@@ -65,10 +67,10 @@ class Frame:
 # ---------------------------------------------------------------------------------------------------------------------
 # convolutions (weights in this project's [K, C_in, C_out] layout)
 
-def dense_weight(w, ksize):
+def dense_weight(w, ksize, dtype=F64):
     """[K, C_in, C_out] -> F.conv3d's [C_out, C_in, kx, ky, kz] on a volume indexed (x, y, z).
     k = 3: offset k = 9 (dz + 1) + 3 (dy + 1) + (dx + 1) (x fastest); k = 2: k = 4 bx + 2 by + bz (z fastest)."""
-    w = _t64(w)
+    w = _t64(w, dtype)
     cin, cout = w.shape[1], w.shape[2]
     if ksize == 3:
         return w.reshape(3, 3, 3, cin, cout).permute(4, 3, 2, 1, 0)       # (dz, dy, dx, ci, co) -> (co, ci, dx, dy, dz)
@@ -76,30 +78,30 @@ def dense_weight(w, ksize):
     return w.reshape(2, 2, 2, cin, cout).permute(4, 3, 0, 1, 2)           # (bx, by, bz, ci, co) -> (co, ci, bx, by, bz)
 
 
-def _bias(bias):
-    return None if bias is None else _t64(bias)
+def _bias(bias, dtype=F64):
+    return None if bias is None else _t64(bias, dtype)
 
 
-def subm_conv3(frame, coords, x, w, stride=1, bias=None):
+def subm_conv3(frame, coords, x, w, stride=1, bias=None, dtype=F64):
     """submanifold k=3 convolution at tensor stride s: out[i] = bias + sum over the 27 offsets o of x[coords[i] + o s] W[o]
     = conv3d (padding 1) on the volume subsampled by s, read at the active sites"""
-    vol = frame.embed(coords, x, stride)
-    return frame.read(F.conv3d(vol, dense_weight(w, 3), _bias(bias), padding=1), coords, stride)
+    vol = frame.embed(coords, x, stride, dtype)
+    return frame.read(F.conv3d(vol, dense_weight(w, 3, dtype), _bias(bias, dtype), padding=1), coords, stride)
 
 
-def down_conv(frame, fine, x, coarse, w, stride=1, bias=None):
+def down_conv(frame, fine, x, coarse, w, stride=1, bias=None, dtype=F64):
     """k2s2 convolution from the fine set at tensor stride s to the coarse set at 2s: out[j] = sum over b in {0,1}^3 of
     x[coarse[j] + b s] W[4 bx + 2 by + bz] = conv3d (stride 2) read at the coarse sites"""
-    vol = frame.embed(fine, x, stride)
-    return frame.read(F.conv3d(vol, dense_weight(w, 2), _bias(bias), stride=2), coarse, 2 * stride)
+    vol = frame.embed(fine, x, stride, dtype)
+    return frame.read(F.conv3d(vol, dense_weight(w, 2, dtype), _bias(bias, dtype), stride=2), coarse, 2 * stride)
 
 
-def up_conv(frame, coarse, x, fine, w, stride=1, bias=None):
+def up_conv(frame, coarse, x, fine, w, stride=1, bias=None, dtype=F64):
     """transposed k2s2 convolution from the coarse set at 2s back to the fine set at s: fine voxel i, child b of its parent
     p, gets x[p] W[4 bx + 2 by + bz] = conv_transpose3d (stride 2) from the coarse set, restricted to the fine set"""
-    vol = frame.embed(coarse, x, 2 * stride)
-    wt = dense_weight(w, 2).transpose(0, 1)                                # conv_transpose3d: [C_in, C_out, kx, ky, kz]
-    return frame.read(F.conv_transpose3d(vol, wt, _bias(bias), stride=2), fine, stride)
+    vol = frame.embed(coarse, x, 2 * stride, dtype)
+    wt = dense_weight(w, 2, dtype).transpose(0, 1)                                # conv_transpose3d: [C_in, C_out, kx, ky, kz]
+    return frame.read(F.conv_transpose3d(vol, wt, _bias(bias, dtype), stride=2), fine, stride)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -143,13 +145,13 @@ def lookup(table_rows, query_rows):
     return np.array([ids.get(r, -1) for r in map(tuple, np.asarray(query_rows, np.int64).reshape(-1, 4).tolist())], np.int64)
 
 
-def scatter_mean(feat, inverse, m):
+def scatter_mean(feat, inverse, m, dtype=F64):
     """float64 mean of the rows of feat per target (index_add_ + counts); rows with target -1 are dropped, empty targets 0"""
-    feat = _t64(feat)
+    feat = _t64(feat, dtype)
     inv = torch.as_tensor(np.asarray(inverse), dtype=torch.int64)
     live = inv >= 0
-    s = torch.zeros((m, feat.shape[1]), dtype=F64).index_add(0, inv[live], feat[live])
-    n = torch.zeros(m, dtype=F64).index_add_(0, inv[live], torch.ones(int(live.sum()), dtype=F64))
+    s = torch.zeros((m, feat.shape[1]), dtype=dtype).index_add(0, inv[live], feat[live])
+    n = torch.zeros(m, dtype=dtype).index_add_(0, inv[live], torch.ones(int(live.sum()), dtype=dtype))
     return s / n.clamp(min=1)[:, None]
 
 
@@ -184,11 +186,11 @@ def corner_tables(vox_coords, stride, scaled_xyzb):
     return idx, w / (w.sum(1, keepdims=True) + 1e-8)
 
 
-def devoxelize(vfeat, idx, w):
+def devoxelize(vfeat, idx, w, dtype=F64):
     """out[p] = sum_k w[p, k] vfeat[idx[p, k]] over the present corners, float64, differentiable in vfeat"""
-    vfeat = _t64(vfeat)
+    vfeat = _t64(vfeat, dtype)
     idx = torch.as_tensor(np.asarray(idx), dtype=torch.int64)
-    w = _t64(w)
+    w = _t64(w, dtype)
     pad = torch.cat([vfeat, vfeat.new_zeros(1, vfeat.shape[1])])
     rows = torch.where(idx >= 0, idx, torch.full_like(idx, vfeat.shape[0]))
     return (pad[rows] * torch.where(idx >= 0, w, torch.zeros_like(w))[:, :, None]).sum(1)
@@ -197,11 +199,11 @@ def devoxelize(vfeat, idx, w):
 # ---------------------------------------------------------------------------------------------------------------------
 # ConvGRU gates (models/modules.py:214-221)
 
-def gate(v, mode, h=None, zg=None):
+def gate(v, mode, h=None, zg=None, dtype=F64):
     """mode 1 sigmoid(v) (update gate z), 2 sigmoid(v) h (r h), 3 (1 - z) h + z tanh(v) (new hidden state), float64"""
-    v = _t64(v)
+    v = _t64(v, dtype)
     if mode == 3:
-        h, zg = _t64(h), _t64(zg)
+        h, zg = _t64(h, dtype), _t64(zg, dtype)
         return (1 - zg) * h + zg * torch.tanh(v)
     r = torch.sigmoid(v)
-    return r * _t64(h) if mode == 2 else r
+    return r * _t64(h, dtype) if mode == 2 else r
