@@ -61,6 +61,8 @@ SIGNATURES = {
     "eprecon_raycast_workspace_bytes": (_sz, [_i64]),
     "eprecon_raycast_build_async": (_i, [_vp, _vp, _i64, _vp, _sz, _vp]),
     "eprecon_raycast_async": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp]),
+    "eprecon_distance_field_workspace_bytes": (_sz, [_i64, _vp, _vp]),
+    "eprecon_distance_field_async": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "eprecon_transpose_map_async": (_i, [_vp, _i64, _vp, _i, _vp, _vp]),
     "eprecon_sparse_conv_async": (_i, [_vp, _i64, _i, _vp, _i, _i64, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
     "eprecon_conv_bn_partial_bytes": (_sz, [_i64, _i]),

@@ -2,7 +2,7 @@
 
     python -m eprecon_amd.reconstruct --data_path DIR [--source_path DIR] [--mode test|val] [--ckpt FILE] --out DIR \\
            [--scenes FILE] [--n_views 9] [--size 640 480] [--host-views] [--color] [--clean N [--clean_segments N]] [--objects]
-           [--simplify CELL] [--preview]
+           [--simplify CELL] [--distance METRES] [--preview]
 
 reads <data_path>/all_tsdf_<n_views>_1/fragments_<mode>.pkl (eprecon_amd.generate_gt writes it) and the frames it names
 (scannet.ScanNetDataset), and walks the fragments in file order, one per step: PrepareViews -> RandomTransformSpace (no
@@ -33,6 +33,10 @@ with its voxel count, centroid, axis-aligned box and upright oriented box (eprec
 --simplify CELL (off by default) writes the three meshes of every saved scene once more, simplified by quadric vertex
 clustering in cells of CELL metres (eprecon_amd.simplify), as <scene>_lod.ply, mesh_semantic_<scene>_lod.ply and
 mesh_instance_<scene>_lod.ply beside them; no other file changes.
+
+--distance METRES (off by default) writes <scene>_distance.npz beside every saved scene once it is written: for every cell
+of the scene's box dilated by METRES the exact squared distance, in cells, to the nearest surface sample within METRES, that
+sample's voxel row and the cell's own state (eprecon_amd.distance_field); no other file changes.
 
 --preview (off by default) writes <out>/preview/<scene>/<fragment_id:05d>.png after every fragment: the scene so far, ray-cast
 from its voxel rows (eprecon_amd.raycast) from that fragment's last key-frame camera at the network's image size, shaded by
@@ -87,6 +91,8 @@ def parse_args(argv=None):
     ap.add_argument("--objects", action="store_true", help="also write <scene>_objects.json: count, centroid and boxes per segment")
     ap.add_argument("--simplify", type=float, metavar="CELL", help="also write the scene's meshes simplified by vertex clustering "
                                                                    "in cells of CELL metres, as *_lod.ply")
+    ap.add_argument("--distance", type=float, metavar="METRES", help="also write <scene>_distance.npz: the distance of every cell "
+                                                                     "to the nearest surface sample within METRES, and its row")
     ap.add_argument("--preview", action="store_true", help="also write preview/<scene>/<fragment_id>.png after every fragment: "
                     "the scene so far, ray-cast from the fragment's last key-frame camera")
     return ap.parse_args(argv)
@@ -167,6 +173,16 @@ def simplify_saved_scenes(outputs, saver, epoch, cell):
         npz = os.path.join(save_path, name.replace("/", "-") + ".npz")
         if os.path.exists(npz):
             print(f"[reconstruct] {format_report(name, simplify_scene(npz, save_path, cell)[0])}")
+
+
+def distance_saved_scenes(outputs, saver, epoch, max_distance):
+    """--distance: the distance fields of the scenes this step saved, as <scene>_distance.npz beside them"""
+    from .distance_field import distance_scene, format_report
+    save_path = "{}_fusion_eval_{}".format(saver.log_dir, epoch)
+    for name in outputs.get("scene_name", []):
+        npz = os.path.join(save_path, name.replace("/", "-") + ".npz")
+        if os.path.exists(npz):
+            print(f"[reconstruct] {format_report(name, distance_scene(npz, save_path, max_distance)[0])}")
 
 
 def preview_fragment(model, inputs, meta, out, voxel_size, stride=4):
@@ -259,6 +275,8 @@ def main(argv=None):
                 describe_saved_scenes(outputs, saver, epoch)
             if args.simplify is not None:
                 simplify_saved_scenes(outputs, saver, epoch, args.simplify)
+            if args.distance is not None:
+                distance_saved_scenes(outputs, saver, epoch, args.distance)
             if args.preview:
                 preview_fragment(model, inputs, meta, args.out, float(cfg.MODEL.VOXEL_SIZE))
             count += 1

@@ -360,6 +360,33 @@ int eprecon_raycast_build_async(const int32_t *coords, const float *tsdf, int64_
 int eprecon_raycast_async(const void *grid, int64_t m, const float *tsdf, const double *cams, int n_views, int height, int width,
                           float pixel_center, float znear, float zfar, int refine, float *depth, float *normal, int32_t *row,
                           int32_t *status, void *stream);
+
+/*
+ * Distance field of a sparse TSDF scene (csrc/distance_field.hip; the rule is DESIGN.md §5b "distance field", the caller
+ * eprecon_amd/distance_field.py): for every cell of the box [lo, hi) the exact squared distance, in cells, to the nearest site
+ * inside the box, and that site's row.
+ *   coords  int32[m,3] voxel rows (no batch column; c - 1 .. c + 1 must be keys of the hash grid), tsdf f32[m].  A row is
+ *           inside when tsdf <= 0, a coordinate that is no row is outside, of rows that repeat a coordinate the first counts;
+ *           a site is a row with a 6-neighbour coordinate whose inside-state differs from its own.  Rows outside the box are
+ *           looked up as neighbours and are no sites of this call.
+ *   lo, hi  host int32[3]; extents X, Y, Z = hi - lo, each 1 .. 1024
+ *   radius  R >= 0 in cells
+ *   dist2   int32[X,Y,Z] (z fastest): min over the sites s of |x - s|^2, exact where it is <= R^2, 0x7fffffff beyond
+ *   site    int32[X,Y,Z]: the smallest row among the sites that attain dist2, -1 beyond R^2
+ *   state   uint8[X,Y,Z]: 0 no row, 1 an outside row, 2 an inside row
+ *   status  int32[1] (device): cleared and written by every call; bit 0 a coordinate outside the key range (the row is left
+ *           out), bit 1 the row table full.  The caller that reads it raises.
+ *   workspace  eprecon_distance_field_workspace_bytes(m, lo, hi) bytes (0 for a box the call would refuse), 256-byte aligned:
+ *           the row table and two volumes of 64-bit keys (d2 << 32) | row.  Nothing is allocated inside.
+ * Six launches whatever the rows look like (clear, insert, seed, and a band-minimum pass along z, y and x); m == 0 fills far
+ * and state 0 in the first and launches nothing else.  No atomics outside the table build, no workgroup waits on another,
+ * integers only: the outputs are bit-identical from run to run.
+ * EPRECON_ERR_ARG: an empty or inverted box, an extent above 1024, radius < 0, a null pointer, a short workspace.
+ */
+size_t eprecon_distance_field_workspace_bytes(int64_t m, const int32_t lo[3], const int32_t hi[3]);
+int eprecon_distance_field_async(const int32_t *coords, const float *tsdf, int64_t m, const int32_t lo[3], const int32_t hi[3],
+                                 int radius, int32_t *dist2, int32_t *site, uint8_t *state, int32_t *status, void *workspace,
+                                 size_t workspace_bytes, void *stream);
 /* ------------------------------------------------------------------------------------------
  * Kernel maps and sparse convolution  (K5, K10, K11, K13)
  *
